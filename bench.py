@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the north-star path: CosyVoice3-0.5B instruct inference, batch 8 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one pass of the hot path (speech-token LM greedy decode -> 10-step CFG flow matching over
@@ -9,8 +9,13 @@ the DiT -> HiFT vocoder) over one batch of 8 synthetic instruct utterances per G
 in HBM, outputs (wavs) copied to host memory inside the timed region; with N > 1 every
 rank runs its own 8 utterances (data-parallel, no data-path collective), one RCCL all-gather collects
 the finished audio and every rank copies it to the host.  `--gpus N` without an outer launcher starts
-its own N ranks (one child `torch.distributed.run`).  After the timed region utterance 0 of the last
-timed step is checked against the CPU oracle ("checked" in the JSON line).
+its own N ranks (one child `torch.distributed.run`).
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`,
+`config`, `host_cpu_ms_per_step`).  `--dump-outputs DIR` then writes what the last timed step delivered
+(rank 0: wav.npy, n_samples.npy, tokens.npy; inputs and weights are seeded, so two builds compare output
+for output).  Everything else is measured with `--full` only: the figures and objects named below, and
+at the end utterance 0 of the last timed step checked against the CPU oracle ("checked" in the JSON line).
 
 Workload (cfg 2 = BASELINE.json configs[1]): instruct text 8 ids + tts text U{10..20} ids,
 5 s prompt (125 speech tokens / 250 mel frames, x-vector 192), forced length n = 75 tokens per
@@ -364,13 +369,32 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def dump_outputs(d, timed):
+    """What the last timed step delivered to rank 0, as .npy files in d: wav.npy (float32, rows x samples: the wavs on the host,
+    every rank's rows after the all-gather), n_samples.npy (float64: each row's valid length) and tokens.npy (float64: this rank's
+    speech-token ids, -1 past an utterance's count).  8 x 3 s of audio per rank = 2.3 MB."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    toks = timed["toks"]
+    ids = np.full((len(toks), max(len(t) for t in toks)), -1.0)
+    for b, t in enumerate(toks):
+        ids[b, : len(t)] = t.reshape(-1).double().numpy()
+    np.save(os.path.join(d, "wav.npy"), timed["wav"].float().numpy())
+    np.save(os.path.join(d, "n_samples.npy"), np.asarray(timed["n_samples"], dtype=np.float64))
+    np.save(os.path.join(d, "tokens.npy"), ids)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary objects (zero-shot batch 4, HiFT-only config 5, ...)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure and check everything else the record can carry: "
+                    "fresh inputs, rooflines, one batch alone, the LM alone, FY_PRECISE, exact weights, the secondary objects, the CPU "
+                    "oracle's baseline and check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step delivered as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's baseline and check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary objects (zero-shot batch 4, HiFT-only config 5, ...)")
     ap.add_argument("--no-pipeline", action="store_true", help="run the steps strictly one after another")
     ap.add_argument("--llm-streams", type=int, default=1, help="LM handles decoding different steps' batches concurrently")
     ap.add_argument("--lm-isolate", action="store_true", help="LM streams run ONLY on the CUs the flow stream is kept off")
@@ -383,6 +407,8 @@ def main():
     ap.add_argument("--flow-group", type=int, default=1, help="consecutive steps whose batches go through the flow decoder + vocoder as ONE ragged batch "
                     "(not the default: the metric's step is a batch of 8; see DESIGN.md section 10)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no outer launcher: start one rank per GPU ourselves (the reference's own multi-GPU inference pattern,
@@ -441,9 +467,11 @@ def main():
 
     def deliver(wav, samples, toks):
         """The metric's end point: all wavs resident on the host - after the all-gather for N > 1."""
+        n_all = samples
         if world > 1:
-            wav, _ = gather_audio(wav.cpu() if rehearsal else wav, samples, b_max=BATCH, s_max=S_MAX, reuse=not rehearsal)   # the GPU path copies the result to the host at once
-        last["wav"], last["toks"], last["mel"] = wav.cpu(), toks, model.last_mel       # D2H inside the timed region
+            wav, per_rank = gather_audio(wav.cpu() if rehearsal else wav, samples, b_max=BATCH, s_max=S_MAX, reuse=not rehearsal)   # the GPU path copies the result to the host at once
+            n_all = [n for r in per_rank for n in r]
+        last["wav"], last["toks"], last["mel"], last["n_samples"] = wav.cpu(), toks, model.last_mel, n_all       # D2H inside the timed region
         return samples
 
     def step():
@@ -483,7 +511,7 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     host_cpu_ms = 1e3 * (time.process_time() - cpu0) / a.steps
-    timed = {k: (v.clone() if torch.is_tensor(v) else [t.cpu() for t in v]) for k, v in last.items()}      # the last timed step's outputs
+    timed = {k: (v.clone() if torch.is_tensor(v) else [t.cpu() if torch.is_tensor(t) else t for t in v]) for k, v in last.items()}      # the last timed step's outputs
     if world > 1:
         t = torch.tensor([dt], device="cpu" if rehearsal else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -491,6 +519,33 @@ def main():
     audio_per_step = world * sum(samples) / 24000.0
     value = audio_per_step * a.steps / dt
     log(f"timed {a.steps} steps: {1e3 * dt / a.steps:.1f} ms/step, {value:.1f} audio_s/s")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, timed)
+
+    out = {
+        "metric": "synthesised audio sec/sec (RTF^-1) CosyVoice3-0.5B instruct, batch 8",
+        "value": round(value, 3), "unit": "audio_s/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(1e3 * dt / a.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": "CosyVoice3-0.5B instruct (inference_instruct2), batch 8 mixed-length utterances per GPU, "
+                               "5 s prompt, 75 forced speech tokens (3 s) each, LM greedy -> 10-step CFG flow (DiT-22) -> HiFT",
+                   "batch_per_gpu": BATCH, "tokens_per_utt": N_TOK, "prompt_tokens": P_TOK, "parallelism": f"dp{world}",
+                   "steps_pipelined": pipelined, "llm_streams": n_llm, "lm_group": group, "flow_workers": a.flow_workers if pipelined else 1, "flow_group": a.flow_group if pipelined else 1,
+                   "lm_rows_per_weight_pass": BATCH * group,
+                   "utterances_in_flight_max": BATCH * (3 * group * n_llm + a.flow_workers) if pipelined else BATCH,
+                   "in_flight_note": "one LM call decodes lm_group steps' batches together; the ids of up to 2 x lm_group finished batches wait in a queue; flow_workers batches are in the flow decoder / vocoder side by side",
+                   "flow_cu_exclude": a.flow_cu_exclude,
+                   "weights": "random-init, CosyVoice3-0.5B shapes (859 M params)"},
+        # CPU time this rank's process spent per timed step, all threads (time.process_time over the timed region): what 8 ranks on
+        # one host need of it (x 8) against the host's cores
+        "host_cpu_ms_per_step": round(host_cpu_ms, 2),
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- the same K steps with FRESH input tensors per step (SURVEY 8d starts the clock at "model_input dicts resident on host"): the
     # prompt cache never hits, every step pads its prompts and copies them to the device (3 H2D copies + a stream wait per batch)
@@ -717,32 +772,17 @@ def main():
             del model2
             torch.cuda.empty_cache()
 
-    out = {
-        "metric": "synthesised audio sec/sec (RTF^-1) CosyVoice3-0.5B instruct, batch 8",
-        "value": round(value, 3), "unit": "audio_s/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(1e3 * dt / a.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": "CosyVoice3-0.5B instruct (inference_instruct2), batch 8 mixed-length utterances per GPU, "
-                               "5 s prompt, 75 forced speech tokens (3 s) each, LM greedy -> 10-step CFG flow (DiT-22) -> HiFT",
-                   "batch_per_gpu": BATCH, "tokens_per_utt": N_TOK, "prompt_tokens": P_TOK, "parallelism": f"dp{world}",
-                   "steps_pipelined": pipelined, "llm_streams": n_llm, "lm_group": group, "flow_workers": a.flow_workers if pipelined else 1, "flow_group": a.flow_group if pipelined else 1,
-                   "lm_rows_per_weight_pass": BATCH * group,
-                   "utterances_in_flight_max": BATCH * (3 * group * n_llm + a.flow_workers) if pipelined else BATCH,
-                   "in_flight_note": "one LM call decodes lm_group steps' batches together; the ids of up to 2 x lm_group finished batches wait in a queue; flow_workers batches are in the flow decoder / vocoder side by side",
-                   "flow_cu_exclude": a.flow_cu_exclude, "batch_latency_ms_unpipelined": round(latency_ms, 1),
-                   "weights": "random-init, CosyVoice3-0.5B shapes (859 M params)"},
+    out["config"]["batch_latency_ms_unpipelined"] = round(latency_ms, 1)
+    out.update({
         # the strict batch-8 figure: one batch at a time, nothing of another batch in flight (tts_batch; LM on the persistent step)
         "value_batch8_unpipelined": round(audio_per_step / (latency_ms * 1e-3), 2),
         "value_fresh_inputs": value_fresh,
-        # CPU time this rank's process spent per timed step, all threads (time.process_time over the timed region): what 8 ranks on
-        # one host need of it (x 8) against the host's cores
-        "host_cpu_ms_per_step": round(host_cpu_ms, 2),
         "roofline": roofline,
         "roofline_lm": roofline_lm,
         "roofline_lm_persistent": roofline_lm_p,
         "precise_mode": precise,
         "exact_weights": exact_w,
-    }
+    })
     if rank == 0 and world == 1 and not a.no_extras:
         # behind the timed region: BASELINE.json configs[0], configs[2] and configs[4] as secondary objects of the same record
         log("one utterance alone (config 1's shape)")

@@ -246,14 +246,35 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FY_BENCH_REHEARSAL="1")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "4", "--no-extras", "--no-cpu-baseline"],
-                       env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "4", "--full", "--no-extras",
+                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["scaling"] == "weak"
     # 2 ranks x 8 utterances x 3 s per step
     assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 2 * 8 * 3.0) < 1e-3
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline record of its --steps timed steps and nothing measured beside it,
+    and --dump-outputs writes what the last timed step delivered: 8 wavs of 3 s, their lengths, 75 token ids each."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                        str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 8 * 3.0) < 1e-3
+    assert not {"roofline", "value_fresh_inputs", "cpu_baseline", "checked"} & set(d)
+    wav, n, ids = (np.load(tmp_path / f) for f in ("wav.npy", "n_samples.npy", "tokens.npy"))
+    assert wav.dtype == np.float32 and n.dtype == np.float64 and ids.dtype == np.float64
+    assert n.tolist() == [72000.0] * 8 and wav.shape[0] == 8 and wav.shape[1] >= 72000 and np.isfinite(wav).all() and 0 < np.abs(wav).max() <= 1.0
+    assert ids.shape == (8, 75) and ids.min() >= 0 and ids.max() < 6561 and (ids == np.round(ids)).all()
 
 
 def test_allgather_audio_c_entry_single_rank(tmp_path):
