@@ -88,6 +88,9 @@ def _declare(L):
     L.fy_hift_decode.argtypes = [vp, f32p, f32p, i32p, i32, i32, f32p, u32, vp]
     L.fy_hift_tap.argtypes = [vp, C.c_char_p, f32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
     L.fy_hift_resblock.argtypes = [vp, i32, f32p, f32p, i32, i32, u32, vp]
+    L.fy_hift_stream_reset.argtypes = [vp]
+    L.fy_hift_stream_samples.argtypes = [vp]
+    L.fy_hift_stream_window.argtypes = [vp]
     L.fy_flow_default_config.argtypes = [C.POINTER(FlowConfig)]
     L.fy_flow_default_config.restype = None
     L.fy_flow_create.argtypes = [C.POINTER(vp), C.POINTER(FlowConfig), C.POINTER(FyTensor), i32, i32, i32, vp]

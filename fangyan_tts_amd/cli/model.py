@@ -661,7 +661,8 @@ class CosyVoice3Model:
         """The reference's chunk schedule: a chunk is cut whenever `hop + pre_lookahead` tokens beyond the offset exist (the
         first hop is padded so prompt + hop is a multiple of 25); every chunk re-runs the flow decoder over all tokens so far
         (chunk attention mask, finalize=False) and the vocoder over the whole mel so far (finalize=False), and yields the
-        samples beyond those already yielded; the last call is finalize=True without the chunk mask.  The reference polls
+        samples beyond those already yielded (here the vocoder computes only those, from the new frames plus a fixed margin:
+        the same samples); the last call is finalize=True without the chunk mask.  The reference polls
         a list its LM thread fills; here the LM is advanced on demand (`LlmEngine.begin` / `step`) by as many tokens as the
         next chunk still lacks, so the first chunk leaves after hop + look-ahead tokens, not after the whole utterance.  The
         chunk boundaries depend only on the token count, so the chunks are the reference's."""
@@ -695,6 +696,7 @@ class CosyVoice3Model:
             pad = -(-n_fp // hop0) * hop0 - n_fp
             offset, speech_offset, mel_all = 0, 0, None
             ln.flow.stream_reset()                          # the incremental flow calls of this stream start from nothing
+            ln.hift.stream_reset()                          # ... and so do the vocoder's
             # The LM runs ahead of the chunks on its own stream and thread (the reference's llm_job): it publishes (tokens kept, done)
             # after every slice of steps - a slice ends with the ids complete in memory (fy_llm_step waits for its stream), so the
             # chunk's stream may read out[:, :n] without an event.  The first slice is what the first chunk lacks.
@@ -711,7 +713,10 @@ class CosyVoice3Model:
                 valid = 2 * (n_in if finalize else n_in - look)
                 mel = mel[:, :, 2 * offset: valid]
                 mel_all = mel if mel_all is None else torch.cat([mel_all, mel], dim=2)
-                wav, _ = ln.hift.inference(mel_all.contiguous(), self.rand_ini, self.sine_noise, finalize=finalize, flags=self.hift_flags)
+                # the vocoder continues its stream (csrc/hift.hip: FY_INCREMENTAL): it runs over the new frames plus a fixed margin and
+                # writes only wav[speech_offset:end] - the same samples as a run over the whole mel so far
+                wav, _ = ln.hift.inference(mel_all.contiguous(), self.rand_ini, self.sine_noise, finalize=finalize, flags=self.hift_flags,
+                                           incremental=True)
                 end = up * (mel_all.shape[2] if finalize else mel_all.shape[2] - 8)
                 return wav[:, speech_offset:end].cpu(), mel_all, end
 

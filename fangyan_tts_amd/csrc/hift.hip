@@ -41,6 +41,12 @@ struct fy_hift {
     ConvW ups_poly[N_UP];                            // ups[i] in polyphase form (conv_pack_polyphase)
     int *lens;                                       // device: [8][max_batch] = F, L0, L1, L2conv, L2, S_out, F_f0, F_dec (set_lens)
     int B = 0, Fmax = 0;                             // of the last call (for taps)
+    // FY_INCREMENTAL stream (B = 1, see hift_infer_incremental): samples delivered so far (0 = the next call computes everything), mel
+    // frames of the stream's last call, mel frames the last call ran through the network, and per harmonic the sine source's running
+    // double sum at the frame where the next call's exact f0 begins (device)
+    long inc_samples = 0;
+    int inc_frames = 0, inc_window = 0;
+    double* inc_phase = nullptr;
     int L(int stage, int F) const {                  // rows of stage tensors for F frames
         int l = F;
         for (int i = 0; i <= stage; ++i) l *= cfg.ups[i];
@@ -214,6 +220,8 @@ extern "C" int fy_hift_create(fy_hift** out, const fy_hift_config* cfg, const fy
     for (int i = 0; i < N_UP; ++i)
         if (h->sb_ld[i]) TRYC(h->pool.alloc(&h->sb[i], B * ((size_t)h->L(i, (int)F) + 1) * h->sb_ld[i]));
     TRYC(h->pool.alloc(&h->lens, 8 * B));
+    TRYC(h->pool.alloc(&h->inc_phase, 16));
+    if (hipMemsetAsync(h->inc_phase, 0, 16 * sizeof(double), st) != hipSuccess) { fy_set_error("fy_hift_create: hipMemsetAsync failed"); return fail(FY_ERR_HIP); }
 #undef TRYC
     if (hipStreamSynchronize(st) != hipSuccess) { fy_set_error("fy_hift_create: stream sync failed"); return fail(FY_ERR_HIP); }
     *out = h;
@@ -240,14 +248,20 @@ __global__ void f0_classifier_k(const float* __restrict__ hin, const float* __re
 // signal returns the frame's own value (source index 480 i + 239.5, both neighbours inside frame i, so
 // rand_ini - added to sample 0 only - never enters); torch.cumsum on CPU accumulates fp32 data in double
 // and rounds each prefix to fp32; phase = ((cum*2)*pi)*480 in fp32; value = sin(phase) * sine_amp.
+// carry (FY_INCREMENTAL, B = 1; else null with a0 = a_next = -1): the running sum across the calls of a stream.  At frame a0 the
+// sum continues from carry[hm], the earlier call's sum over every frame before a0 (the frames before a0 start from 0 and feed only
+// samples the call does not keep); the sum over the frames before a_next is stored there for the next call.  The same sequential
+// double additions as one call over the whole utterance, so the same bits.
 __global__ void sine_phase_k(const float* __restrict__ f0, float* __restrict__ sines, const int* __restrict__ frames,
-                             int Fmax, int H1, float sr, float amp, float up) {
+                             int Fmax, int H1, float sr, float amp, float up, double* __restrict__ carry, int a0, int a_next) {
     int b = blockIdx.x, hm = threadIdx.x;
     if (hm >= H1) return;
     int n = frames[b];
     double cum = 0.0;
     const float mult = (float)(hm + 1);
     for (int t = 0; t < n; ++t) {
+        if (t == a0) cum = carry[hm];
+        if (t == a_next) carry[hm] = cum;
         float fn = f0[(long)b * Fmax + t] * mult;
         float q = fn / sr;
         float rad = q - floorf(q);                  // torch '%' on floats: result takes the divisor's sign; q >= 0 here
@@ -259,12 +273,14 @@ __global__ void sine_phase_k(const float* __restrict__ f0, float* __restrict__ s
         ph = ph * up;
         sines[((long)b * Fmax + t) * H1 + hm] = sinf(ph) * amp;
     }
+    if (n == a_next) carry[hm] = cum;
 }
 
-// SineGen2.forward :303-316 + SourceModuleHnNSF.forward :367-368, per sample.
+// SineGen2.forward :303-316 + SourceModuleHnNSF.forward :367-368, per sample.  n0: the utterance's sample of row 0 (a window
+// that starts at mel frame W reads the fixed sine_waves table from sample 480 W on).
 __global__ void source_k(const float* __restrict__ f0, const float* __restrict__ sines, const float* __restrict__ noise,
                          const float* __restrict__ lw, const float* __restrict__ lb, float* __restrict__ src,
-                         const int* __restrict__ frames, int Fmax, int H1, int up, float thr, float sigma, float amp) {
+                         const int* __restrict__ frames, int Fmax, int H1, int up, float thr, float sigma, float amp, long n0) {
     int b = blockIdx.y;
     long n = blockIdx.x * 256L + threadIdx.x;
     long S = (long)frames[b] * up;
@@ -275,7 +291,7 @@ __global__ void source_k(const float* __restrict__ f0, const float* __restrict__
     float namp = uv * sigma + ((1.f - uv) * amp) / 3.f;
     float acc = lb[0];
     for (int hm = 0; hm < H1; ++hm) {
-        float sw = sines[((long)b * Fmax + t) * H1 + hm] * uv + namp * noise[n * H1 + hm];
+        float sw = sines[((long)b * Fmax + t) * H1 + hm] * uv + namp * noise[(n0 + n) * H1 + hm];
         acc = fmaf(sw, lw[hm], acc);
     }
     src[(long)b * Fmax * up + n] = tanhf(acc);
@@ -360,11 +376,12 @@ __global__ void spec_k(const float* __restrict__ post, float* __restrict__ spec,
     o[9 + k] = mag * sinf(ph);
 }
 
-// torch.istft(center=True) + clamp, generator.py:503-505, 710: one thread per output sample.
+// torch.istft(center=True) + clamp, generator.py:503-505, 710: one thread per output sample.  Samples [n_lo, s_out) of the
+// rows computed go to wav + b * wav_bs + wav_off (a window's samples land at their place in the utterance).
 __global__ void istft16_k(const float* __restrict__ spec, float* __restrict__ wav, const int* __restrict__ frames, const int* __restrict__ s_out,
-                          int Fmax, int up, int spf, float limit) {
+                          int Fmax, int spf, float limit, int n_lo, long wav_bs, long wav_off) {
     int b = blockIdx.y;
-    long n = blockIdx.x * 256L + threadIdx.x;
+    long n = n_lo + blockIdx.x * 256L + threadIdx.x;
     if (n >= s_out[b]) return;                // a streaming chunk holds its last frame of samples back
     int T = frames[b] * spf + 1;
     int m = (int)n + 8;                       // index in the un-trimmed overlap-add buffer
@@ -385,7 +402,7 @@ __global__ void istft16_k(const float* __restrict__ spec, float* __restrict__ wa
         env += w * w;
     }
     y = y / env;
-    wav[(long)b * Fmax * up + n] = fminf(fmaxf(y, -limit), limit);
+    wav[b * wav_bs + wav_off + n] = fminf(fmaxf(y, -limit), limit);
 }
 
 // __constant__ tables are per device: filled once per device (idempotent, so two handles' first calls may both do it)
@@ -449,7 +466,9 @@ static int run_conv(const ConvDesc& d, const ConvW& w, uint32_t flags, hipStream
     return conv1d_f32_direct(d, w, st);
 }
 
-static int hift_f0(fy_hift* h, int B, int Fmax, hipStream_t st) {
+// L_pick: the length that picks the fp32 MFMA kernel's form (conv1d_f32_mfma: by L_out; the two forms sum the input channels in
+// different orders) - a window of an FY_INCREMENTAL call passes the whole call's, so its rows are summed as the whole call sums them
+static int hift_f0(fy_hift* h, int B, int Fmax, hipStream_t st, int L_pick = 0) {
     const fy_hift_config& c = h->cfg;
     const int* lF = h->lens;                               // mel frames
     const int* lF0 = h->lens + 6 * h->max_batch;           // f0 frames (= mel frames unless a streaming chunk)
@@ -460,7 +479,7 @@ static int hift_f0(fy_hift* h, int B, int Fmax, hipStream_t st) {
     for (int i = 0; i < 5; ++i) {
         ConvDesc d = base_desc(B);
         d.x = in; d.x_bs = (long)Fmax * in_ld; d.x_ld = in_ld; d.L_in = Fmax; d.in_len = i == 0 ? lF : lF0;
-        d.y = bufs[i & 1]; d.y_bs = (long)Fmax * c.f0_ch; d.y_ld = c.f0_ch; d.L_out = Fmax; d.out_len = lF0;
+        d.y = bufs[i & 1]; d.y_bs = (long)Fmax * c.f0_ch; d.y_ld = c.f0_ch; d.L_out = std::max(Fmax, L_pick); d.out_len = lF0;
         d.Cin = i == 0 ? c.mel : c.f0_ch; d.Cout = c.f0_ch; d.KW = h->w.f0c[i].KW;
         d.pad_left = i == 0 ? 0 : (d.KW - 1);
         d.bias = h->w.f0c[i].bias; d.post_act = ACT_ELU;
@@ -472,14 +491,16 @@ static int hift_f0(fy_hift* h, int B, int Fmax, hipStream_t st) {
     return FY_OK;
 }
 
-static int hift_source(fy_hift* h, const float* f0, int B, int Fmax, const float* rand_ini, const float* sine_noise, hipStream_t st) {
+// carry / a0 / a_next / n0: the FY_INCREMENTAL window (sine_phase_k, source_k); null / -1 / -1 / 0 for a whole call
+static int hift_source(fy_hift* h, const float* f0, int B, int Fmax, const float* rand_ini, const float* sine_noise, hipStream_t st,
+                       double* carry = nullptr, int a0 = -1, int a_next = -1, long n0 = 0) {
     const fy_hift_config& c = h->cfg;
     (void)rand_ini;   // provably without effect on the output (see sine_phase_k); kept in the ABI for fidelity
     const int H1 = c.harmonics + 1;
     hipLaunchKernelGGL(sine_phase_k, dim3(B), dim3(64), 0, st, f0, h->rad_phase, h->lens + 6 * h->max_batch, Fmax, H1, (float)c.sampling_rate,
-                       c.nsf_alpha, (float)h->up_total);
+                       c.nsf_alpha, (float)h->up_total, carry, a0, a_next);
     hipLaunchKernelGGL(source_k, dim3(cdiv(Fmax * h->up_total, 256), B), dim3(256), 0, st, f0, h->rad_phase, sine_noise, h->lin_w,
-                       h->lin_b, h->source, h->lens + 6 * h->max_batch, Fmax, H1, h->up_total, c.voiced_thr, c.nsf_sigma, c.nsf_alpha);
+                       h->lin_b, h->source, h->lens + 6 * h->max_batch, Fmax, H1, h->up_total, c.voiced_thr, c.nsf_sigma, c.nsf_alpha, n0);
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }
@@ -574,7 +595,8 @@ __global__ void reflect_row0_k(float* __restrict__ y, const float* __restrict__ 
         if (rs.ya[k]) rs.ya[k][(long)b * bs + c] = f32_to_bf16(snake_fast(v, rs.al[k][c]));
 }
 
-static int hift_decode(fy_hift* h, int B, int Fmax, float* wav, uint32_t flags, hipStream_t st) {
+// n_lo / wav_off: the iSTFT writes samples [n_lo, S_out) of the rows computed, at wav + wav_off (FY_INCREMENTAL windows)
+static int hift_decode(fy_hift* h, int B, int Fmax, float* wav, uint32_t flags, hipStream_t st, int n_lo = 0, long wav_off = 0) {
     const fy_hift_config& c = h->cfg;
     const int mb = h->max_batch;
     const int spf = h->stft_per_frame, up = h->up_total;
@@ -672,7 +694,8 @@ static int hift_decode(fy_hift* h, int B, int Fmax, float* wav, uint32_t flags, 
     }
     // the spectrum overwrites s_stft (no longer needed)
     hipLaunchKernelGGL(spec_k, dim3(cdiv(Tmax * 9, 256), B), dim3(256), 0, st, h->post, h->s_stft, h->lens + 7 * mb, Fmax, spf);
-    hipLaunchKernelGGL(istft16_k, dim3(cdiv(Fmax * up, 256), B), dim3(256), 0, st, h->s_stft, wav, h->lens + 7 * mb, h->lens + 5 * mb, Fmax, up, spf, c.audio_limit);
+    hipLaunchKernelGGL(istft16_k, dim3(cdiv(std::max(Fmax * up - n_lo, 1), 256), B), dim3(256), 0, st, h->s_stft, wav, h->lens + 7 * mb, h->lens + 5 * mb, Fmax, spf,
+                       c.audio_limit, n_lo, (long)Fmax * up, wav_off);
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }
@@ -681,10 +704,115 @@ static int load_mel(fy_hift* h, const float* mel, int B, int Fmax, hipStream_t s
     return transpose_bcl_to_blc(mel, h->mel_cl, B, h->cfg.mel, Fmax, (long)h->cfg.mel * Fmax, (long)Fmax * h->cfg.mel, h->cfg.mel, st);
 }
 
+// one utterance's mel (C, ld), frames [f_lo, f_lo + L) -> channels-last (L, C): load_mel over an FY_INCREMENTAL window
+__global__ void mel_window_k(const float* __restrict__ src, float* __restrict__ dst, int C, int L, int ld, int f_lo) {
+    __shared__ float tile[32][33];
+    const int c0 = blockIdx.y * 32, l0 = blockIdx.x * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int i = ty; i < 32; i += 8) {
+        const int c = c0 + i, l = l0 + tx;
+        tile[i][tx] = (c < C && l < L) ? src[(long)c * ld + f_lo + l] : 0.f;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+        const int l = l0 + i, c = c0 + tx;
+        if (c < C && l < L) dst[(long)l * C + c] = tile[tx][i];
+    }
+}
+
+// frames of f0 history: the k3 convs after condnet[0] zero-pad on the left, so a window's first frames of f0 are not the stream's
+static int hift_f0_history(const fy_hift* h) {
+    int n = 0;
+    for (int i = 1; i < 5; ++i) n += h->w.f0c[i].KW - 1;
+    return n;
+}
+
+static long floor_div(long a, long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }     // b > 0
+
+// ---- FY_INCREMENTAL: the vocoder over a window of the stream ------------------------------------------------------------------
+// CausalHiFTGenerator is causal, so samples [P, ...) depend on the mel frames from some frame on only; a call of the stream runs the
+// whole pipeline over mel[:, W:F] and keeps the samples beyond those the stream has delivered.  hift_window_start gives the largest W
+// whose run reproduces every sample from P on.  It walks the receptive field back from sample P, stage by stage, from the config:
+//   iSTFT (the first frame overlapping P) <- conv_post (k - 1 rows) <- the stage-2 ResBlocks (the deepest: (k - 1) x sum(d + 1)) <- the
+//   reflect-padded up-conv (one row of offset, k - 1 up-sampled rows) ... down to conv_pre (no history: 4 frames of look-ahead);
+//   and from every stage's fused rows through its source ResBlock and strided source down-sampler (2s taps, s - 1 rows of left
+//   padding) to the STFT frames, the source samples they read (hop t - n_fft / 2 on, centred), and the f0 frames of those samples.
+//   The f0 predictor's k3 convs (2 frames of history each) zero-pad at the window's left edge, so f0 is exact from W + 8 on: the
+//   source frames must start there.  Every left edge the window itself makes (zero padding, the stage-2 ReflectionPad1d((1,0)),
+//   the centred STFT's reflect padding, the iSTFT envelope's first frames) then lies before what the kept samples read.
+// For CosyVoice3's config: W = P / 480 - 37 - the source path of stage 0 (15-row super-rows under a k7
+// source ResBlock) reaches 29 frames back, and 8 more for the f0 history; the decoder path only 22.
+// Window alignment: no rounding.  W is any frame: a row's arithmetic in these kernels does not depend on where the row sits in its
+// tile (conv1d_bf16_mfma_k, resblock_iter_k, the polyphase up-conv and the super-row source_downs sum taps outer / 16-channel steps
+// inner for every row alike; the fp32-MFMA f0 convs alike; halo rows are recomputed with the same order), and every stage's
+// rows shift by whole rows (8 W, 40 W, 120 W; the super-rows by 120 W / s with s | 120).  The one length-dependent choice, the
+// f0 convs' kernel form, follows the whole call's length (hift_f0's L_pick).
+static long hift_window_start(const fy_hift* h, long P) {
+    const fy_hift_config& c = h->cfg;
+    if (P <= 0) return 0;
+    int dsum = 0, rb_hist = 0;
+    for (int m = 0; m < N_DIL; ++m) dsum += c.rb_d[m] + 1;
+    for (int j = 0; j < N_RB; ++j) rb_hist = std::max(rb_hist, (c.rb_k[j] - 1) * dsum);
+    const int half = c.n_fft / 2;
+    long r = floor_div(P + half - (c.n_fft - 1) + c.hop - 1, c.hop);      // first iSTFT frame that overlaps sample P
+    r -= h->w.conv_post.KW - 1;                                             // conv_post's causal taps: the last stage's ResBlock output
+    long x = r - rb_hist;                                                   // the last stage's fused rows (up-conv + source)
+    long stft = x, pre = 0;
+    for (int i = N_UP - 1; i >= 0; --i) {
+        int k, s;
+        source_down_shape(c, i, &k, &s);
+        const long sd = x - (c.src_rb_k[i] - 1) * dsum;                     // source ResBlock
+        stft = std::min(stft, s * sd - (s - 1));                            // output p reads STFT rows s p - (s - 1) ..
+        const long q = x - (i == N_UP - 1 ? 1 : 0);                         // the last stage's ReflectionPad1d((1,0)) shifts its rows by one
+        const long prev = floor_div(q - (c.up_k[i] - 1), c.ups[i]);          // nearest x ups then k - 1 causal taps
+        if (i > 0) x = prev - rb_hist; else pre = prev;
+    }
+    const long src_frame = floor_div((long)c.hop * stft - half, h->up_total);
+    return std::max(0L, std::min(pre, src_frame - hift_f0_history(h)));
+}
+
+static int hift_infer_incremental(fy_hift* h, const float* mel, const int32_t* frames, int32_t B, int32_t Fmax, const float* rand_ini,
+                                  const float* sine_noise, float* wav, float* source, uint32_t flags, hipStream_t st) {
+    FY_CHECK(B == 1, FY_ERR_ARG, "fy_hift_infer: FY_INCREMENTAL streams one utterance (B = 1, got %d)", B);
+    FY_CHECK(!source, FY_ERR_ARG, "fy_hift_infer: FY_INCREMENTAL computes only the new samples and returns no source (pass null)");
+    FY_CHECK(frames && Fmax >= 1 && Fmax <= h->max_frames && frames[0] >= 1 && frames[0] <= Fmax, FY_ERR_ARG,
+             "fy_hift_infer: frames %d / Fmax %d outside the handle's limit %d", frames ? frames[0] : 0, Fmax, h->max_frames);
+    const bool finalize = !(flags & FY_NO_FINALIZE);
+    const int F = frames[0], up = h->up_total;
+    // continue the stream, or start over (after fy_hift_stream_reset or a finalize call, or when the mel shrank)
+    const long S_prev = F >= h->inc_frames ? h->inc_samples : 0;
+    const long S_out = (long)(finalize ? F : F - 8) * up;
+    const int W = (int)hift_window_start(h, S_prev);
+    const int Fw = F - W, f0h = hift_f0_history(h);
+    // the sine source: from frame a0 (the window's first exact f0 frame) the phase sums continue the stream's; the sums at the next
+    // call's a0 are stored (they lie inside this call's exactly computed f0 frames, checked)
+    const int a0 = W > 0 ? f0h : -1;
+    int a_next = -1;
+    if (!finalize) {
+        const long Wn = hift_window_start(h, S_out);
+        if (Wn > 0) a_next = (int)(Wn + f0h - W);
+        FY_CHECK(a_next < 0 || (a_next >= std::max(a0, 0) && a_next <= Fw - (h->w.f0c[0].KW - 1)), FY_ERR_STATE,
+                 "fy_hift_infer: the next window's phase anchor %d lies outside this call's exact f0 frames", a_next);
+    }
+    FY_TRY(set_lens(h, &Fw, 1, Fw, st, finalize));      // (a chunk's minimum length)
+    FY_CHECK(S_out >= S_prev, FY_ERR_STATE, "fy_hift_infer: FY_INCREMENTAL call ends before the samples already delivered");
+    h->inc_samples = 0; h->inc_frames = 0;              // a call that fails below leaves no stream to continue (the phase sums may be gone)
+    dim3 grid(cdiv(Fw, 32), cdiv(h->cfg.mel, 32));
+    hipLaunchKernelGGL(mel_window_k, grid, dim3(256), 0, st, mel, h->mel_cl, h->cfg.mel, Fw, Fmax, W);
+    HIP_TRY(hipGetLastError());
+    FY_TRY(hift_f0(h, 1, Fw, st, Fmax));
+    FY_TRY(hift_source(h, h->f0, 1, Fw, rand_ini, sine_noise, st, h->inc_phase, a0, a_next, (long)W * up));
+    FY_TRY(hift_decode(h, 1, Fw, wav, flags, st, (int)(S_prev - (long)W * up), (long)W * up));
+    h->inc_window = Fw;
+    h->inc_samples = finalize ? 0 : S_out;
+    h->inc_frames = finalize ? 0 : F;
+    return FY_OK;
+}
+
 extern "C" int fy_hift_infer(fy_hift* h, const float* mel, const int32_t* frames, int32_t B, int32_t Fmax, const float* rand_ini,
                              const float* sine_noise, float* wav, float* source, uint32_t flags, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     FY_CHECK(h && mel && sine_noise && wav, FY_ERR_ARG, "fy_hift_infer: null argument");
+    if (flags & FY_INCREMENTAL) return hift_infer_incremental(h, mel, frames, B, Fmax, rand_ini, sine_noise, wav, source, flags, st);
     FY_TRY(set_lens(h, frames, B, Fmax, st, !(flags & FY_NO_FINALIZE)));
     FY_TRY(load_mel(h, mel, B, Fmax, st));
     FY_TRY(hift_f0(h, B, Fmax, st));
@@ -692,6 +820,16 @@ extern "C" int fy_hift_infer(fy_hift* h, const float* mel, const int32_t* frames
     if (source) HIP_TRY(hipMemcpyAsync(source, h->source, (size_t)B * Fmax * h->up_total * sizeof(float), hipMemcpyDeviceToDevice, st));
     return hift_decode(h, B, Fmax, wav, flags, st);
 }
+
+extern "C" int fy_hift_stream_reset(fy_hift* h) {
+    FY_CHECK(h, FY_ERR_ARG, "fy_hift_stream_reset: null handle");
+    h->inc_samples = 0; h->inc_frames = 0; h->inc_window = 0;
+    return FY_OK;
+}
+
+extern "C" int fy_hift_stream_samples(const fy_hift* h) { return h ? (int)h->inc_samples : -1; }
+
+extern "C" int fy_hift_stream_window(const fy_hift* h) { return h ? h->inc_window : -1; }
 
 extern "C" int fy_hift_f0(fy_hift* h, const float* mel, const int32_t* frames, int32_t B, int32_t Fmax, float* f0, void* stream) {
     hipStream_t st = (hipStream_t)stream;

@@ -12,7 +12,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import FY_DIRECT, FY_NO_FINALIZE, FY_PRECISE, check  # noqa: F401
+from ._lib import FY_DIRECT, FY_INCREMENTAL, FY_NO_FINALIZE, FY_PRECISE, check  # noqa: F401
 from .spec import HiftCfg
 
 
@@ -68,13 +68,19 @@ class HiftEngine:
         return mel, B, Fmax, _lib.int_array(frames)
 
     def inference(self, speech_feat: torch.Tensor, rand_ini: torch.Tensor, sine_noise: torch.Tensor,
-                  frames: Optional[Sequence[int]] = None, flags: int = 0, want_source: bool = False, finalize: bool = True):
+                  frames: Optional[Sequence[int]] = None, flags: int = 0, want_source: bool = False, finalize: bool = True,
+                  incremental: bool = False):
         """speech_feat (B, 80, Fmax) -> (wav (B, 480*Fmax), source (B, 1, 480*Fmax) or None).
         Samples past 480*frames[b] of a shorter utterance are left untouched (zeros).
         finalize=False (generator.py:713-726, a streaming chunk): 3 + 4 frames are look-ahead and one frame of samples is held
-        back: utterance b is valid in wav[b, :480*(frames[b] - 8)], its source in [:480*(frames[b] - 3)]."""
+        back: utterance b is valid in wav[b, :480*(frames[b] - 8)], its source in [:480*(frames[b] - 3)].
+        incremental (one utterance, the whole mel so far): this call continues the handle's stream - only the samples beyond those
+        the stream has delivered are computed and written, wav[:, stream_samples() before the call : the end above]; the rest
+        stays zero.  Same values as without the flag.  A finalize call ends the stream; `stream_reset` starts a new one."""
         if not finalize:
             flags |= FY_NO_FINALIZE
+        if incremental:
+            flags |= FY_INCREMENTAL                     # (with want_source the library refuses: there is no whole source)
         mel, B, Fmax, fr = self._prep(speech_feat, frames)
         S = Fmax * self.cfg.upsample_total
         assert sine_noise.is_cuda and sine_noise.is_contiguous() and sine_noise.shape[-2] >= S
@@ -83,6 +89,18 @@ class HiftEngine:
         check(_lib.lib().fy_hift_infer(self._h, mel.data_ptr(), fr, B, Fmax, rand_ini.data_ptr(), sine_noise.data_ptr(),
                                        wav.data_ptr(), src.data_ptr() if want_source else None, flags, self._stream()))
         return wav, (src[:, None] if want_source else None)
+
+    def stream_reset(self):
+        """Forget the incremental stream: the next incremental call starts a new one."""
+        check(_lib.lib().fy_hift_stream_reset(self._h))
+
+    def stream_samples(self) -> int:
+        """Samples the incremental calls of the current stream have delivered (0: the next call computes everything)."""
+        return int(_lib.lib().fy_hift_stream_samples(self._h))
+
+    def stream_window(self) -> int:
+        """Mel frames the last incremental call ran through the network."""
+        return int(_lib.lib().fy_hift_stream_window(self._h))
 
     def f0(self, speech_feat, frames=None):
         mel, B, Fmax, fr = self._prep(speech_feat, frames)

@@ -70,7 +70,14 @@ int fy_stream_destroy(void* stream);
                              on a chunk boundary (the reference's schedule does).  After fy_flow_stream_reset, when the prompt lengths differ
                              from the previous call's or the token count shrank, everything is computed and kept for the next call; a call
                              whose length is not a whole number of chunks is computed whole and keeps NOTHING (the next call starts over).
-                             Same results as without the flag.                                                                         */
+                             Same results as without the flag.
+                             HiFT, B = 1, with or without FY_NO_FINALIZE (and with FY_DIRECT / FY_PRECISE): the call continues the handle's
+                             stream.  It takes the whole mel so far (frames[0] = F) and the same wav layout, runs the vocoder over the
+                             frames from a fixed margin before the samples already delivered (S_prev) only, and writes only wav[S_prev,
+                             S_out) - S_out = 480 (F - 8) for a chunk, 480 F for a finalize call - the same bits the call without the flag
+                             writes there; samples before S_prev are left untouched.  A finalize call ends the stream; a call after
+                             fy_hift_stream_reset or with fewer frames than the previous call computes everything (same result as without
+                             the flag).  source must be null.                                                                          */
 #define FY_NO_FINALIZE 8u /* flow, HiFT: a streaming chunk (finalize=False in the reference): the last tokens / frames are
                             look-ahead context, not output (flow: pre_lookahead tokens; HiFT: 3 + 4 frames and 480 samples) */
 
@@ -117,6 +124,14 @@ int fy_hift_tap(fy_hift* h, const char* name, float* dst, int64_t* rows, int64_t
 /* one ResBlock (generator.py:110-117) of the main stack, index 0..8, on x (B, L, C) channels-last, in -> out.
  * The microbenchmark entry for BASELINE config 5.                                                           */
 int fy_hift_resblock(fy_hift* h, int32_t index, const float* x, float* y, int32_t B, int32_t L, uint32_t flags, void* stream);
+
+/* forget the FY_INCREMENTAL stream: the next incremental call starts a new one (call it when a stream=True generation begins) */
+int fy_hift_stream_reset(fy_hift* h);
+/* samples the incremental calls of the current stream have delivered; 0 = nothing (the next call computes everything) */
+int fy_hift_stream_samples(const fy_hift* h);
+/* mel frames the last FY_INCREMENTAL call ran through the network (its window: F on a stream's first call, then the new frames plus a
+ * fixed margin - 37 frames for CosyVoice3's config) */
+int fy_hift_stream_window(const fy_hift* h);
 
 /* ============================ flow-matching decoder ============================
  * replaces CausalMaskedDiffWithDiT.inference(token, ..., prompt_feat, embedding, streaming, finalize=True)
