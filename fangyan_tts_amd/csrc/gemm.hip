@@ -3,6 +3,7 @@
 #include "runtime.h"
 #include <algorithm>
 #include <atomic>
+#include <stdio.h>
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 frag_ab;
@@ -1098,6 +1099,8 @@ static int gemm_launch2(const void* A, int lda, const bf16_t* W, int M, int N, i
     //   128x128 (3), 32x32x16 / 16x16x32    58.7 / 56.1  27.6 / 24.3  51.5 / 48.8  42.3 / 37.0   (M 3200: 18.8 / 19.8 and 29.4 / 31.3)
     //   256x256 (1), plain / staggered      72.9 / 70.1  38.3 / 36.4  45.1 / 42.2  62.6 / 58.8   300 tiles: two rounds
     //   320x256 (1), staggered                 47.5         44.0         49.1         70.1       240 tiles: one round
+    // Round 7 (profiles/r07_gemm_resid_tiling.txt): out / ff2 at M = 6400 take gemm64_k's 256x128 tiles, 16 waves (override 6412) -
+    // alone 26.7 / 37.4 us against ~25.5 / 38-42 for the 128x128 ring, in the pipelined benchmark 3.4-3.6 % less time per step (comment below).
     // All tilings give bit-identical outputs (K is accumulated in the same order; checked by gemm_bench).
     // the ring kernels' direct epilogue stores 16 consecutive columns per lane in 16-byte pieces
     const bool ring_ok = (((uintptr_t)epi.out | (uintptr_t)epi.out_lo | (uintptr_t)epi.resid) & 15) == 0 && epi.ldc % 8 == 0 &&
@@ -1111,7 +1114,9 @@ static int gemm_launch2(const void* A, int lda, const bf16_t* W, int M, int N, i
         }
         const bf16_t* Ab = (const bf16_t*)A;
         static const int env_ov = getenv("FY_GEMM_TILE") ? atoi(getenv("FY_GEMM_TILE")) : 0;   // experiments: a tiling for every product
-        const int ov = gemm_tile_override ? gemm_tile_override : env_ov;
+        // FY_GEMM_TILE_EPI<n>: the same for the products of one epilogue (0 bf16 / rotary, 1 GELU, 3 gated residual) only
+        static const int env_ove = [] { char n[24]; snprintf(n, sizeof n, "FY_GEMM_TILE_EPI%d", EPI); return getenv(n) ? atoi(getenv(n)) : 0; }();
+        const int ov = gemm_tile_override ? gemm_tile_override : (env_ove ? env_ove : env_ov);
         if (ov == 256 && N % 256 == 0) return gemm_launch_256<EPI, 256>(Ab, lda, W, M, N, K, epi, st);
         if (ov == 320 && N % 256 == 0) return gemm_launch_256<EPI, 256, 320>(Ab, lda, W, M, N, K, epi, st);
         if (ov == 1256 && N % 256 == 0) return gemm_launch_256<EPI, 256, 256, 1>(Ab, lda, W, M, N, K, epi, st);
@@ -1135,11 +1140,18 @@ static int gemm_launch2(const void* A, int lda, const bf16_t* W, int M, int N, i
             }
         }
         if constexpr (EPI == 3) {
-            // the gated fp32 residual products (out-projection, ff2) as 256 x 128 tiles of 16 waves, one per CU: measured, NOT chosen
-            // (override 6412 only).  Its K loop takes what the 128 x 128 LDS-DMA tiles' takes (15.6 against 15.4 us for the
-            // out-projection, 31.9 against 30.6 for ff2): sixteen 32 x 64 wave tiles read 0.75 fragments per MFMA and, with the staging
-            // stores, the LDS array is busier than the matrix cores - and one tile per CU has nothing to run under its epilogue.
-            if (ov == 6412 && K % 64 == 0) return gemm_launch_64<EPI, 256, 128, 16>(Ab, lda, W, M, N, K, epi, st);
+            // the gated fp32 residual products (out-projection, ff2) as 256 x 128 tiles of 16 waves, one per CU (override 6412), when
+            // those tiles cover half the chip or more in one round (M = 6400: 200 tiles).  ALONE it is no faster than the 128 x 128
+            // LDS-DMA tiles (out 26.7 against ~25.5 us, ff2 37.4 against 38-42; its K loop 15.6 against 15.4 us per tile: sixteen
+            // 32 x 64 wave tiles read 0.75 fragments per MFMA).  But it does a 128 x 128 tile's work twice per K loop, so it holds a CU
+            // for half the time per output, and in the pipelined benchmark the second flow stream's kernels take the CUs it leaves:
+            // 47.7 -> 46.1 ms per step (profiles/r07_gemm_resid_tiling.txt).  FY_GEMM_RESID64=0: the 128 x 128 tiles.
+            // Trials, bit-identical and not kept: the 128 x 128 ring with four / five stages (no faster alone), 256 x 128
+            // tiles of the 32-deep ring two per CU (2002: 47.1 ms per step).
+            static const int r64 = getenv("FY_GEMM_RESID64") ? atoi(getenv("FY_GEMM_RESID64")) : 1;
+            const int t6412 = (N / 128) * cdiv(M, 256);
+            if ((ov == 6412 || (ov == 0 && r64 && t6412 <= cus && 2 * t6412 >= cus)) && K % 64 == 0)
+                return gemm_launch_64<EPI, 256, 128, 16>(Ab, lda, W, M, N, K, epi, st);
         }
         // 320x256 tiles, one workgroup per CU, when they cover the chip in ONE round where 256x128 tiles would need a second one
         if (ov == 1320 && N % 256 == 0) return gemm_launch_256<EPI, 256, 320, 1>(Ab, lda, W, M, N, K, epi, st);
@@ -1284,6 +1296,21 @@ extern "C" int fy_debug_gemm_bf16(const void* A, const void* W, int32_t M, int32
     GemmEpi e;
     e.bias = bias; e.out = out; e.out_bf16 = 1; e.ldc = N; e.act = gelu ? ACT_GELU_TANH : ACT_NONE;
     if (rope) { e.rope = reinterpret_cast<const float2*>(rope); e.rope_T = rope_T; e.rope_half = 32; e.rope_stride = N / 3; }   // the DiT's qkv: head 0 of q and of k
+    const int was = gemm_tile_override;
+    gemm_tile_override = tile;
+    const int rc = gemm_bf16((const bf16_t*)A, K, (const bf16_t*)W, M, N, K, e, (hipStream_t)stream);
+    gemm_tile_override = was;
+    return rc;
+}
+
+// test hook (tests/test_gemm_tilings_m6400_gpu.py): resid [M][N] fp32 += gate * (A [M][K] bf16 x W [N][K] bf16 + bias), the gated residual
+// of the out-projection and ff2, with one tiling forced (gemm_launch2's override codes; 0 = the automatic choice).  h_bf16 / ln_slots
+// (both or neither): also the folded LayerNorm's producer side - bf16 of the new residual and per-64-column (sum, sum of squares) slots
+extern "C" int fy_debug_gemm_resid(const void* A, const void* W, int32_t M, int32_t N, int32_t K, const float* bias, const float* gate, float* resid,
+                                   void* h_bf16, void* ln_slots, int32_t tile, void* stream) {
+    GemmEpi e;
+    e.mode = EPI_GATE_RESID; e.bias = bias; e.gate = gate; e.resid = resid; e.ldc = N;
+    e.h_bf16 = (bf16_t*)h_bf16; e.ln_slots = (float2*)ln_slots;
     const int was = gemm_tile_override;
     gemm_tile_override = tile;
     const int rc = gemm_bf16((const bf16_t*)A, K, (const bf16_t*)W, M, N, K, e, (hipStream_t)stream);
