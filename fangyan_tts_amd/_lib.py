@@ -112,6 +112,13 @@ def _declare(L):
     L.fy_llm_prefill.argtypes = [vp, vp, i32, i32p, i32p, i32p, i32, vp, i32, vp]
     L.fy_llm_step.argtypes = [vp, i32, vp, i32, vp, vp, i32p, vp]
     L.fy_llm_logp.argtypes = [vp, i32, f32p, vp]
+    L.fy_llm_slots_open.argtypes = [vp, vp, i32, vp]
+    L.fy_llm_slot_join.argtypes = [vp, i32p, i32, i32p, i32p, i32p, i32p, i32p, i32p, vp]
+    L.fy_llm_slot_join_embeds.argtypes = [vp, i32p, i32, vp, i32, i32p, i32p, i32p, vp]
+    L.fy_llm_slot_release.argtypes = [vp, i32, vp]
+    L.fy_llm_slots_live.argtypes = [vp, i32p]
+    L.fy_llm_slots_steps.argtypes = [vp]
+    L.fy_llm_slots_steps.restype = C.c_int64
     L.fy_prompt_mel_create.argtypes = [C.POINTER(vp), i32, vp]
     L.fy_prompt_mel_destroy.argtypes = [vp]
     L.fy_prompt_mel_destroy.restype = None

@@ -71,6 +71,15 @@ struct fy_llm {
     bf16_t *img_h = nullptr, *img_ao = nullptr, *img_act = nullptr;
     float *ssq = nullptr, *part32 = nullptr;
     int *cnt32 = nullptr;
+    // decode slots (fy_llm_slots_open): sequences join and leave between token steps; fy_llm_begin / fy_llm_prefill close the session
+    bool slots_open = false;
+    std::vector<int> slot_state;           // per slot: 0 free, 1 running, 2 ended (seen by a step) and not yet released
+    int32_t* slot_out = nullptr;           // the session's (max_batch, slot_out_ld) ids, row = slot
+    int slot_out_ld = 0;
+    int ssq_rpad = 32;                     // the row stride ssq currently stands in (32 ceil(rows of the next step / 32))
+    long slot_steps = 0;                   // token steps launched in this session
+    float* h_live = nullptr;               // [max_batch][hidden]: the running slots' next inputs while a join uses h as workspace
+    int* slot_map = nullptr;               // [max_batch]: logits row of a join -> slot
     int n_speech() const { return cfg.speech_tokens + 200; }
     int qkv_dim() const { return (cfg.q_heads + 2 * cfg.kv_heads) * cfg.head_dim; }
     size_t cache_layer() const { return (size_t)max_batch * cfg.kv_heads * max_ctx * cfg.head_dim; }
@@ -173,12 +182,14 @@ __device__ __forceinline__ void next_image(const NextImg& ni, const float* __res
 // st rows: 0 pos, 1 raw_n, 2 n_out, 3 done, 4 silent run, 5 min_len, 6 max_len.
 __global__ __launch_bounds__(256) void sample_k(const float* __restrict__ logits, int n_all, int n_real, int* __restrict__ st, int mb,
                                                 int* __restrict__ out_ids, int out_ld, const float* __restrict__ semb,
-                                                float* __restrict__ h, int H, float* __restrict__ logp_keep, int keep_step, NextImg ni) {
+                                                float* __restrict__ h, int H, float* __restrict__ logp_keep, int keep_step, NextImg ni,
+                                                const int* __restrict__ slot_map) {
     __shared__ float sv[256];
     __shared__ int si[256];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    // logits row blockIdx.x belongs to slot b: the identity in a decode step, slot_map in a slot join (everything else is per slot)
+    const int b = slot_map ? slot_map[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
     if (st[3 * mb + b]) return;
-    const float* x = logits + (long)b * n_all;
+    const float* x = logits + (long)blockIdx.x * n_all;
     // the row is read once into registers (all loads in flight together), the three passes run on registers
     constexpr int PER = 32;                                  // 256 x 32 = 8192 >= speech vocabulary + 200
     float xv[PER];
@@ -269,7 +280,8 @@ __global__ __launch_bounds__(256) void sample_ras_k(const float* __restrict__ lo
                                                     int* __restrict__ out_ids, int out_ld, const float* __restrict__ semb,
                                                     float* __restrict__ h, int H, float* __restrict__ logp_keep, int keep_step,
                                                     const float* __restrict__ uni, long n_uni, int* __restrict__ recent,
-                                                    int top_k, float top_p, int win, float rep_thr, NextImg ni) {
+                                                    int top_k, float top_p, int win, float rep_thr, NextImg ni,
+                                                    const int* __restrict__ slot_map) {
     extern __shared__ float pl[];                            // softmax(logp) in index order
     __shared__ float sv[256];
     __shared__ int si[256];
@@ -278,9 +290,9 @@ __global__ __launch_bounds__(256) void sample_ras_k(const float* __restrict__ lo
     __shared__ int cand_i[32];
     __shared__ int sh_n, sh_id, sh_flag, sh_cnt;
     __shared__ float sh_u;
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = slot_map ? slot_map[blockIdx.x] : blockIdx.x, tid = threadIdx.x;       // as in sample_k
     if (st[3 * mb + b]) return;
-    const float* x = logits + (long)b * n_all;
+    const float* x = logits + (long)blockIdx.x * n_all;
     constexpr int PER = 32;
     float xv[PER];
 #pragma unroll
@@ -439,6 +451,53 @@ __global__ __launch_bounds__(256) void sample_ras_k(const float* __restrict__ lo
         st[1 * mb + b] = raw_n + 1;
         st[0 * mb + b] += 1;
         if (raw_n + 1 >= st[6 * mb + b]) st[3 * mb + b] = 1;
+    }
+}
+
+// ---- decode slots (fy_llm_slots_open / fy_llm_slot_join / fy_llm_slot_release): a sequence owns column `slot` of st and of
+// `recent`, row `slot` of the uniforms, of out_ids, of h (its next input embedding) and of the A image / sums of squares, and
+// sequence `slot` of the KV cache.  A join prefills into free slots while the others wait between two token steps. ------------
+// The values of a join travel as kernel arguments (no table is copied): up to 32 sequences per launch.
+struct SlotJoinArgs {
+    int n = 0, j0 = 0;                   // sequences in this launch, and the index of its first one in the join
+    int slot[32], start[32], len[32], min_len[32], max_len[32];
+};
+// rows of the packed prefill -> (cache sequence = slot, position); last_row / slot_map for the head and the sampler
+__global__ void slot_rows_k(SlotJoinArgs a, int* __restrict__ row_seq, int* __restrict__ row_pos, int* __restrict__ last_row, int* __restrict__ slot_map) {
+    const int j = blockIdx.x, s = a.slot[j];
+    for (int p = threadIdx.x; p < a.len[j]; p += blockDim.x) { row_seq[a.start[j] + p] = s; row_pos[a.start[j] + p] = p; }
+    if (threadIdx.x == 0) { last_row[s] = a.start[j] + a.len[j] - 1; slot_map[a.j0 + j] = s; }
+}
+// the joined slots' own columns of st and recent: nothing of a previous occupant stays
+__global__ void slot_state_k(SlotJoinArgs a, int* __restrict__ st, int mb, int* __restrict__ recent, int win) {
+    const int j = blockIdx.x, s = a.slot[j];
+    if (threadIdx.x < 8) {
+        const int r = threadIdx.x;
+        st[r * mb + s] = r == 0 ? a.len[j] - 1 : r == 5 ? a.min_len[j] : r == 6 ? a.max_len[j] : 0;
+    }
+    if (recent) for (int k = threadIdx.x; k < win; k += blockDim.x) recent[k * mb + s] = 0;
+}
+__global__ void gather_slot_rows_k(const float* __restrict__ src, const int* __restrict__ last_row, const int* __restrict__ slot_map, float* __restrict__ dst, int H) {
+    const long r = last_row[slot_map[blockIdx.x]];
+    for (int c = threadIdx.x; c < H; c += blockDim.x) dst[(long)blockIdx.x * H + c] = src[r * H + c];
+}
+__global__ void copy_rows_k(const float* __restrict__ src, float* __restrict__ dst, long n) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = src[i];
+}
+// The running slots' operands after a join used h / img_h / ssq as prefill workspace: h[b] back from the copy made before it
+// (src == h: no copy, only the image - the step's row count moved to another ssq layout), and the A image and sums of squares
+// from that row with the sampler's own arithmetic (next_image), so they are the bits the sampler left.
+__global__ __launch_bounds__(256) void slot_restore_k(const float* __restrict__ src, float* __restrict__ h, const int* __restrict__ st, int mb, int H, NextImg ni) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (st[3 * mb + b]) return;
+    if (src != h) for (int c = tid; c < H; c += 256) h[(long)b * H + c] = src[(long)b * H + c];
+    next_image(ni, src + (long)b * H, b, H, tid);
+}
+// fy_llm_slots_open: every slot free (done), nothing counted; fy_llm_slot_release: the same for one slot
+__global__ void slot_free_k(int* __restrict__ st, int mb, int slot) {
+    for (int i = threadIdx.x; i < 8 * mb; i += blockDim.x) {
+        const int r = i / mb, b = i % mb;
+        if (slot < 0 || b == slot) st[i] = r == 3 ? 1 : 0;
     }
 }
 
@@ -716,6 +775,7 @@ extern "C" int fy_llm_create(fy_llm** out, const fy_llm_config* cfg, const fy_te
     hipLaunchKernelGGL(fill_k, dim3(cdiv(std::max(2 * I, l->qkv_dim()), 256)), dim3(256), 0, st, l->ones, 1.0f, std::max(2 * I, l->qkv_dim()));
     TRYC(l->pool.alloc(&l->row_seq, R)); TRYC(l->pool.alloc(&l->row_pos, R)); TRYC(l->pool.alloc(&l->row_src, R));
     TRYC(l->pool.alloc(&l->last_row, B)); TRYC(l->pool.alloc(&l->st, 8 * B)); TRYC(l->pool.alloc(&l->seq_ids, B));
+    TRYC(l->pool.alloc(&l->h_live, B * H)); TRYC(l->pool.alloc(&l->slot_map, B));
     {
         std::vector<int> ids(B);
         for (size_t i = 0; i < B; ++i) ids[i] = (int)i;
@@ -857,40 +917,43 @@ static int llm_layers(fy_llm* l, int R, const int* row_seq, const int* row_pos, 
     return FY_OK;
 }
 
-static int llm_sample(fy_llm* l, int B, int32_t* out_ids, int out_ld, int keep_step, hipStream_t st);
+// slot_map (device, a join): logits row j belongs to slot slot_map[j] and rpad is the session's ssq row stride; null: row b is slot b
+static int llm_sample(fy_llm* l, int B, int32_t* out_ids, int out_ld, int keep_step, hipStream_t st, const int* slot_map = nullptr, int rpad = 0);
 // have_img: the A image of (norm.weight x rows) and its sums of squares already stand in img_h / ssq (the last layer's down
 // projection left them: a decode step on the 32-row path)
-static int llm_head_and_sample(fy_llm* l, int B, const float* rows, int32_t* out_ids, int out_ld, int keep_step, hipStream_t st, bool have_img = false) {
+static int llm_head(fy_llm* l, int B, const float* rows, hipStream_t st, bool have_img = false) {
     const fy_llm_config& c = l->cfg;
     const int H = c.hidden, NS = l->n_speech();
     if (l->gv32) {
         if (!have_img) FY_TRY(gv32_split_rows(rows, H, B, H, l->norm_w, l->img_h, l->ssq, st));
         Gv32Args a;
         a.W = l->w_head; a.W_lo = l->w_head_lo; a.img = l->img_h; a.R = B; a.N = NS; a.K = H; a.ssq = l->ssq; a.n_ssq = H / 32; a.eps = c.rms_eps; a.y = l->logits; a.ldy = NS;
-        FY_TRY(gemv32(a, st));
-        return llm_sample(l, B, out_ids, out_ld, keep_step, st);
+        return gemv32(a, st);
     }
     GemvArgs a;              // final RMSNorm fused into the llm_decoder product
     a.W = l->w_head; a.x = rows; a.ldx = H; a.R = B; a.N = NS; a.K = H; a.y = l->logits; a.ldy = NS;
     a.norm_w = l->norm_w; a.eps = c.rms_eps;
-    FY_TRY(gemv_bf16w(a, st));
+    return gemv_bf16w(a, st);
+}
+static int llm_head_and_sample(fy_llm* l, int B, const float* rows, int32_t* out_ids, int out_ld, int keep_step, hipStream_t st, bool have_img = false) {
+    FY_TRY(llm_head(l, B, rows, st, have_img));
     return llm_sample(l, B, out_ids, out_ld, keep_step, st);
 }
 
 // logits (B, n_speech) -> the sampler: token, stop flags, silent-token filter, next input embedding into h
-static int llm_sample(fy_llm* l, int B, int32_t* out_ids, int out_ld, int keep_step, hipStream_t st) {
+static int llm_sample(fy_llm* l, int B, int32_t* out_ids, int out_ld, int keep_step, hipStream_t st, const int* slot_map, int rpad) {
     const fy_llm_config& c = l->cfg;
     const int H = c.hidden, NS = l->n_speech();
     FY_CHECK(NS <= 256 * 32, FY_ERR_ARG, "sample: %d logits exceed the kernel's register tile", NS);
     NextImg ni;              // the next decode step's first operand (32-row path): image of ln1[0] x speech_embedding[id]
-    if (l->gv32) { ni.img = l->img_h; ni.ssq = l->ssq; ni.ln = l->L[0].ln1; ni.Rpad = 32 * cdiv(B, 32); }
+    if (l->gv32) { ni.img = l->img_h; ni.ssq = l->ssq; ni.ln = l->L[0].ln1; ni.Rpad = rpad ? rpad : 32 * cdiv(B, 32); }
     if (l->sampler == 1)
         hipLaunchKernelGGL(sample_ras_k, dim3(B), dim3(256), (size_t)NS * sizeof(float), st, l->logits, NS, c.speech_tokens, l->st, l->max_batch,
                            out_ids, out_ld, l->speech_emb, l->h, H, l->logp_keep, keep_step < FY_LLM_KEEP_LOGP ? keep_step : -1,
-                           l->uniforms, l->n_uniforms, l->recent, l->top_k, l->top_p, l->win_size, l->rep_thr, ni);
+                           l->uniforms, l->n_uniforms, l->recent, l->top_k, l->top_p, l->win_size, l->rep_thr, ni, slot_map);
     else
         hipLaunchKernelGGL(sample_k, dim3(B), dim3(256), 0, st, l->logits, NS, c.speech_tokens, l->st, l->max_batch, out_ids, out_ld,
-                           l->speech_emb, l->h, H, l->logp_keep, keep_step < FY_LLM_KEEP_LOGP ? keep_step : -1, ni);
+                           l->speech_emb, l->h, H, l->logp_keep, keep_step < FY_LLM_KEEP_LOGP ? keep_step : -1, ni, slot_map);
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }
@@ -927,36 +990,31 @@ static int llm_begin_rows(fy_llm* l, const int* n_rows, const int32_t* min_len, 
     return FY_OK;
 }
 
-extern "C" int fy_llm_begin(fy_llm* l, const int32_t* text_ids, const int32_t* n_text_all, const int32_t* prompt_speech,
-                            const int32_t* n_prompt_speech, const int32_t* min_len, const int32_t* max_len, int32_t B,
-                            int32_t* out_ids, int32_t out_ld, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    FY_CHECK(l && text_ids && n_text_all && n_prompt_speech && min_len && max_len && out_ids, FY_ERR_ARG, "fy_llm_generate: null argument");
-    l->step_next = l->steps_cap = 0;
-    l->all_done = false;
-    FY_CHECK(B >= 1 && B <= l->max_batch && out_ld >= 1, FY_ERR_ARG, "fy_llm_generate: batch %d outside [1, %d]", B, l->max_batch);
+// lm_input = [sos, embed(prompt_text + text), task_id, speech_embedding(prompt_speech)], llm.py:732-740, as row sources for
+// embed_rows_k (src) and the row count per sequence (rows); checks every length and id (who: the entry's name in messages)
+static int llm_lm_input_rows(const fy_llm* l, const char* who, const int32_t* text_ids, const int32_t* n_text_all, const int32_t* prompt_speech,
+                             const int32_t* n_prompt_speech, const int32_t* min_len, const int32_t* max_len, int B, std::vector<int>& src,
+                             std::vector<int>& rows) {
     const fy_llm_config& c = l->cfg;
-    const int H = c.hidden;
-    // lm_input = [sos, embed(prompt_text + text), task_id, speech_embedding(prompt_speech)], llm.py:732-740
-    std::vector<int> src, rows(B, 0);
+    rows.assign(B, 0);
     int to = 0, po = 0;
     for (int b = 0; b < B; ++b) {
         const int nt = n_text_all[b], np = n_prompt_speech[b], Lb = 2 + nt + np;
-        FY_CHECK(nt >= 1 && np >= 0 && min_len[b] >= 0 && max_len[b] >= 1, FY_ERR_ARG, "fy_llm_generate: sequence %d has bad lengths", b);
-        FY_CHECK(Lb + max_len[b] <= l->max_ctx, FY_ERR_ARG, "fy_llm_generate: sequence %d needs %d positions, the handle has %d", b,
+        FY_CHECK(nt >= 1 && np >= 0 && min_len[b] >= 0 && max_len[b] >= 1, FY_ERR_ARG, "%s: sequence %d has bad lengths", who, b);
+        FY_CHECK(Lb + max_len[b] <= l->max_ctx, FY_ERR_ARG, "%s: sequence %d needs %d positions, the handle has %d", who, b,
                  Lb + max_len[b], l->max_ctx);
-        FY_CHECK(np == 0 || prompt_speech, FY_ERR_ARG, "fy_llm_generate: prompt_speech is null");
+        FY_CHECK(np == 0 || prompt_speech, FY_ERR_ARG, "%s: prompt_speech is null", who);
         for (int p = 0; p < Lb; ++p) {
             int s;
             if (p == 0) s = c.speech_tokens | (1 << 30);
             else if (p <= nt) {
                 int id = text_ids[to + p - 1];
-                FY_CHECK(id >= 0 && id < c.vocab, FY_ERR_ARG, "fy_llm_generate: text id %d outside the vocabulary", id);
+                FY_CHECK(id >= 0 && id < c.vocab, FY_ERR_ARG, "%s: text id %d outside the vocabulary", who, id);
                 s = id;
             } else if (p == nt + 1) s = (c.speech_tokens + 2) | (1 << 30);
             else {
                 int id = prompt_speech[po + p - nt - 2];
-                FY_CHECK(id >= 0 && id < l->n_speech(), FY_ERR_ARG, "fy_llm_generate: prompt speech id %d out of range", id);
+                FY_CHECK(id >= 0 && id < l->n_speech(), FY_ERR_ARG, "%s: prompt speech id %d out of range", who, id);
                 s = id | (1 << 30);
             }
             src.push_back(s);
@@ -964,8 +1022,23 @@ extern "C" int fy_llm_begin(fy_llm* l, const int32_t* text_ids, const int32_t* n
         rows[b] = Lb;
         to += nt; po += np;
     }
+    FY_CHECK((int)src.size() <= l->max_rows, FY_ERR_ARG, "%s: %d prefill rows exceed the workspace (%d)", who, (int)src.size(), l->max_rows);
+    return FY_OK;
+}
+
+extern "C" int fy_llm_begin(fy_llm* l, const int32_t* text_ids, const int32_t* n_text_all, const int32_t* prompt_speech,
+                            const int32_t* n_prompt_speech, const int32_t* min_len, const int32_t* max_len, int32_t B,
+                            int32_t* out_ids, int32_t out_ld, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(l && text_ids && n_text_all && n_prompt_speech && min_len && max_len && out_ids, FY_ERR_ARG, "fy_llm_generate: null argument");
+    l->step_next = l->steps_cap = 0;
+    l->all_done = false;
+    l->slots_open = false;
+    FY_CHECK(B >= 1 && B <= l->max_batch && out_ld >= 1, FY_ERR_ARG, "fy_llm_generate: batch %d outside [1, %d]", B, l->max_batch);
+    const int H = l->cfg.hidden;
+    std::vector<int> src, rows;
+    FY_TRY(llm_lm_input_rows(l, "fy_llm_generate", text_ids, n_text_all, prompt_speech, n_prompt_speech, min_len, max_len, B, src, rows));
     const int R = (int)src.size();
-    FY_CHECK(R <= l->max_rows, FY_ERR_ARG, "fy_llm_generate: %d prefill rows exceed the workspace (%d)", R, l->max_rows);
     HIP_TRY(hipMemcpyAsync(l->row_src, src.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(stream_wait(st));                        // src dies with this frame
     hipLaunchKernelGGL(embed_rows_k, dim3(R), dim3(256), 0, st, l->row_src, l->embed_tokens, l->embed_tokens_f32, l->speech_emb, l->h, H);
@@ -983,6 +1056,7 @@ extern "C" int fy_llm_prefill(fy_llm* l, const void* embeds, int32_t dtype, cons
     FY_CHECK(l && embeds && n_rows && min_len && max_len && out_ids && (dtype == 0 || dtype == 1), FY_ERR_ARG, "fy_llm_prefill: bad argument (dtype 0 = fp32, 1 = bf16)");
     l->step_next = l->steps_cap = 0;
     l->all_done = false;
+    l->slots_open = false;
     FY_CHECK(B >= 1 && B <= l->max_batch && out_ld >= 1, FY_ERR_ARG, "fy_llm_prefill: batch %d outside [1, %d]", B, l->max_batch);
     const int H = l->cfg.hidden;
     long R = 0;
@@ -999,11 +1073,28 @@ extern "C" int fy_llm_prefill(fy_llm* l, const void* embeds, int32_t dtype, cons
     return llm_begin_rows(l, n_rows, min_len, max_len, B, out_ids, out_ld, st);
 }
 
+// one token step for rows 0 .. B-1 on the path the decode mode and B select (persistent / persistent32: see fy_llm_step)
+static int llm_token_step(fy_llm* l, int B, bool persistent, bool persistent32, int32_t* out_ids, int out_ld, int keep_step, hipStream_t st) {
+    if (persistent) {                    // the 24 layers + llm_decoder of the step in one launch, then the sampler
+        FY_TRY(decode_step(l->dec, B, l->h, l->st, l->inv_freq, l->logits, st));
+        return llm_sample(l, B, out_ids, out_ld, keep_step, st);
+    }
+    if (persistent32) {                  // the same in one launch on a few CUs for up to 32 sequences (operands: the 32-row path's images)
+        FY_TRY(decode32_step(l->dec32, B, l->h, l->img_h, l->ssq, l->qkv, l->img_ao, l->st, l->inv_freq, l->logits, st));
+        return llm_sample(l, B, out_ids, out_ld, keep_step, st);
+    }
+    FY_TRY(llm_layers(l, B, l->seq_ids, l->st, true, st));
+    return llm_head_and_sample(l, B, l->h, out_ids, out_ld, keep_step, st, l->gv32);
+}
+
+static int llm_step_slots(fy_llm* l, int n_steps, int32_t* out_ids, int out_ld, int32_t* out_n, int32_t* raw_n, int32_t* finished, hipStream_t st);
+
 // decode: row b = sequence b at position st[pos][b]; everything a step needs is on the device
 extern "C" int fy_llm_step(fy_llm* l, int32_t n_steps, int32_t* out_ids, int32_t out_ld, int32_t* out_n, int32_t* raw_n,
                            int32_t* finished, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     FY_CHECK(l && out_ids && out_n && out_ld >= 1 && n_steps >= 0, FY_ERR_ARG, "fy_llm_step: bad argument");
+    if (l->slots_open) return llm_step_slots(l, n_steps, out_ids, out_ld, out_n, raw_n, finished, st);
     FY_CHECK(l->step_next >= 1, FY_ERR_STATE, "fy_llm_step: no generation in progress (call fy_llm_begin first)");
     const int mb = l->max_batch, B = l->B;
     const int end = l->all_done ? l->step_next : (int)std::min<long>((long)l->step_next + n_steps, l->steps_cap);
@@ -1028,16 +1119,7 @@ extern "C" int fy_llm_step(fy_llm* l, int32_t n_steps, int32_t* out_ids, int32_t
         return FY_OK;
     };
     for (; step < end; ++step) {
-        if (persistent) {                    // the 24 layers + llm_decoder of the step in one launch, then the sampler
-            FY_TRY(decode_step(l->dec, B, l->h, l->st, l->inv_freq, l->logits, st));
-            FY_TRY(llm_sample(l, B, out_ids, out_ld, step, st));
-        } else if (persistent32) {           // the same in one launch on a few CUs for up to 32 sequences (operands: the 32-row path's images)
-            FY_TRY(decode32_step(l->dec32, B, l->h, l->img_h, l->ssq, l->qkv, l->img_ao, l->st, l->inv_freq, l->logits, st));
-            FY_TRY(llm_sample(l, B, out_ids, out_ld, step, st));
-        } else {
-            FY_TRY(llm_layers(l, B, l->seq_ids, l->st, true, st));
-            FY_TRY(llm_head_and_sample(l, B, l->h, out_ids, out_ld, step, st, l->gv32));
-        }
+        FY_TRY(llm_token_step(l, B, persistent, persistent32, out_ids, out_ld, step, st));
         if ((step & 7) == 7) {
             FY_TRY(read_done());
             bool all = true;
@@ -1065,6 +1147,212 @@ extern "C" int fy_llm_step(fy_llm* l, int32_t n_steps, int32_t* out_ids, int32_t
             FY_CHECK(used[b] <= l->n_uniforms, FY_ERR_ARG, "fy_llm_generate: sequence %d needed %d uniforms, %ld were supplied", b, used[b], l->n_uniforms);
         }
     }
+    return FY_OK;
+}
+
+// ---- decode slots --------------------------------------------------------------------------------------------------------
+static NextImg llm_next_img(const fy_llm* l, int rpad) {
+    NextImg ni;
+    if (l->gv32) { ni.img = l->img_h; ni.ssq = l->ssq; ni.ln = l->L[0].ln1; ni.Rpad = rpad; }
+    return ni;
+}
+// rows of a step: the highest running slot + 1 (slots that ended stay frozen on the device and need no row above the last running one)
+static int llm_slot_rows(const fy_llm* l) {
+    int B = 0;
+    for (int b = 0; b < l->max_batch; ++b) if (l->slot_state[b] == 1) B = b + 1;
+    return B;
+}
+
+extern "C" int fy_llm_slots_open(fy_llm* l, int32_t* out_ids, int32_t out_ld, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(l && out_ids && out_ld >= 1, FY_ERR_ARG, "fy_llm_slots_open: bad argument");
+    l->step_next = l->steps_cap = 0;         // a fy_llm_begin generation in progress is void
+    l->all_done = false;
+    hipLaunchKernelGGL(slot_free_k, dim3(1), dim3(256), 0, st, l->st, l->max_batch, -1);
+    HIP_TRY(hipGetLastError());
+    l->slot_state.assign(l->max_batch, 0);
+    l->slot_out = out_ids; l->slot_out_ld = out_ld;
+    l->ssq_rpad = 32; l->slot_steps = 0; l->B = 0;
+    l->slots_open = true;
+    return FY_OK;
+}
+
+extern "C" int fy_llm_slots_live(const fy_llm* l, int32_t* state) {
+    if (!l || !l->slots_open) {
+        if (l && state) for (int b = 0; b < l->max_batch; ++b) state[b] = 0;
+        return 0;
+    }
+    int n = 0;
+    for (int b = 0; b < l->max_batch; ++b) {
+        if (state) state[b] = l->slot_state[b];
+        n += l->slot_state[b] != 0;
+    }
+    return n;
+}
+
+extern "C" int64_t fy_llm_slots_steps(const fy_llm* l) { return l && l->slots_open ? l->slot_steps : 0; }
+
+extern "C" int fy_llm_slot_release(fy_llm* l, int32_t slot, void* stream) {
+    FY_CHECK(l && l->slots_open, FY_ERR_STATE, "fy_llm_slot_release: no slot session is open (call fy_llm_slots_open first)");
+    FY_CHECK(slot >= 0 && slot < l->max_batch, FY_ERR_ARG, "fy_llm_slot_release: slot %d outside [0, %d)", slot, l->max_batch);
+    FY_CHECK(l->slot_state[slot] != 0, FY_ERR_STATE, "fy_llm_slot_release: slot %d is free", slot);
+    hipLaunchKernelGGL(slot_free_k, dim3(1), dim3(256), 0, (hipStream_t)stream, l->st, l->max_batch, slot);
+    HIP_TRY(hipGetLastError());
+    l->slot_state[slot] = 0;
+    return FY_OK;
+}
+
+// every check of a join, before any device work: the session, the slots, the lengths
+static int llm_join_check(const fy_llm* l, const char* who, const int32_t* slots, int n, const int* n_rows, const int32_t* min_len, const int32_t* max_len) {
+    FY_CHECK(l->slots_open, FY_ERR_STATE, "%s: no slot session is open (call fy_llm_slots_open first)", who);
+    FY_CHECK(n >= 1 && n <= l->max_batch, FY_ERR_ARG, "%s: %d sequences outside [1, %d]", who, n, l->max_batch);
+    long R = 0;
+    for (int j = 0; j < n; ++j) {
+        const int s = slots[j];
+        FY_CHECK(s >= 0 && s < l->max_batch, FY_ERR_ARG, "%s: slot %d outside [0, %d)", who, s, l->max_batch);
+        for (int i = 0; i < j; ++i) FY_CHECK(slots[i] != s, FY_ERR_ARG, "%s: slot %d named twice", who, s);
+        FY_CHECK(l->slot_state[s] == 0, FY_ERR_STATE, "%s: slot %d is live (release it first)", who, s);
+        FY_CHECK(n_rows[j] >= 1 && min_len[j] >= 0 && max_len[j] >= 1, FY_ERR_ARG, "%s: sequence %d has bad lengths", who, j);
+        FY_CHECK(n_rows[j] + max_len[j] <= l->max_ctx, FY_ERR_ARG, "%s: sequence %d needs %d positions, the handle has %d", who, j,
+                 n_rows[j] + max_len[j], l->max_ctx);
+        R += n_rows[j];
+    }
+    FY_CHECK(R <= l->max_rows, FY_ERR_ARG, "%s: %ld prefill rows exceed the workspace (%d)", who, R, l->max_rows);
+    return FY_OK;
+}
+// the running slots' next inputs leave h before the join's rows enter it
+static int llm_join_save(fy_llm* l, hipStream_t st) {
+    const int Bs = llm_slot_rows(l);
+    if (Bs == 0) return FY_OK;
+    const long n = (long)Bs * l->cfg.hidden;
+    hipLaunchKernelGGL(copy_rows_k, dim3((unsigned)std::min<long>(1024, (n + 255) / 256)), dim3(256), 0, st, l->h, l->h_live, n);
+    HIP_TRY(hipGetLastError());
+    return FY_OK;
+}
+// Common tail of the joins: the n sequences' rows stand packed in l->h (n_rows[j] each).  Prefill into the caches of their slots,
+// the first token of each, and the running slots' operands back in place.
+static int llm_join_rows(fy_llm* l, const int32_t* slots, int n, const int* n_rows, const int32_t* min_len, const int32_t* max_len, hipStream_t st) {
+    const fy_llm_config& c = l->cfg;
+    const int mb = l->max_batch, H = c.hidden;
+    const int Bs = llm_slot_rows(l);         // rows whose operands the prefill is about to overwrite
+    int Bn = Bs, R = 0;
+    for (int j = 0; j < n; ++j) Bn = std::max(Bn, slots[j] + 1);
+    const int rpad = 32 * cdiv(Bn, 32);      // the layout the next step (Bn rows) reads ssq in
+    std::vector<SlotJoinArgs> parts;
+    for (int j0 = 0; j0 < n; j0 += 32) {
+        SlotJoinArgs a;
+        a.n = std::min(32, n - j0); a.j0 = j0;
+        for (int j = 0; j < a.n; ++j) {
+            a.slot[j] = slots[j0 + j]; a.start[j] = R; a.len[j] = n_rows[j0 + j]; a.min_len[j] = min_len[j0 + j]; a.max_len[j] = max_len[j0 + j];
+            R += n_rows[j0 + j];
+        }
+        for (int j = a.n; j < 32; ++j) a.slot[j] = a.start[j] = a.len[j] = a.min_len[j] = a.max_len[j] = 0;
+        parts.push_back(a);
+    }
+    for (const SlotJoinArgs& a : parts) hipLaunchKernelGGL(slot_rows_k, dim3(a.n), dim3(256), 0, st, a, l->row_seq, l->row_pos, l->last_row, l->slot_map);
+    if (l->gv32 && !llm_prefill_by_gemm(l, R)) FY_TRY(gv32_split_rows(l->h, H, R, H, l->L[0].ln1, l->img_h, l->ssq, st));
+    FY_TRY(llm_layers(l, R, l->row_seq, l->row_pos, false, st));
+    hipLaunchKernelGGL(gather_slot_rows_k, dim3(n), dim3(256), 0, st, l->h, l->last_row, l->slot_map, l->hb, H);
+    FY_TRY(llm_head(l, n, l->hb, st));
+    // the workspace is free again: first the running slots (st still marks the joined ones as free), then the joined slots' state
+    if (Bs > 0) hipLaunchKernelGGL(slot_restore_k, dim3(Bs), dim3(256), 0, st, l->h_live, l->h, l->st, mb, H, llm_next_img(l, rpad));
+    for (const SlotJoinArgs& a : parts) hipLaunchKernelGGL(slot_state_k, dim3(a.n), dim3(64), 0, st, a, l->st, mb, l->sampler == 1 ? l->recent : nullptr, l->win_size);
+    HIP_TRY(hipGetLastError());
+    FY_TRY(llm_sample(l, n, l->slot_out, l->slot_out_ld, -1, st, l->slot_map, rpad));
+    for (int j = 0; j < n; ++j) l->slot_state[slots[j]] = 1;
+    l->ssq_rpad = rpad;
+    l->B = Bn;
+    return FY_OK;
+}
+
+extern "C" int fy_llm_slot_join(fy_llm* l, const int32_t* slots, int32_t n, const int32_t* text_ids, const int32_t* n_text_all,
+                                const int32_t* prompt_speech, const int32_t* n_prompt_speech, const int32_t* min_len, const int32_t* max_len,
+                                void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(l && slots && text_ids && n_text_all && n_prompt_speech && min_len && max_len, FY_ERR_ARG, "fy_llm_slot_join: null argument");
+    FY_CHECK(l->slots_open, FY_ERR_STATE, "fy_llm_slot_join: no slot session is open (call fy_llm_slots_open first)");
+    FY_CHECK(n >= 1 && n <= l->max_batch, FY_ERR_ARG, "fy_llm_slot_join: %d sequences outside [1, %d]", n, l->max_batch);
+    std::vector<int> src, rows;
+    FY_TRY(llm_lm_input_rows(l, "fy_llm_slot_join", text_ids, n_text_all, prompt_speech, n_prompt_speech, min_len, max_len, n, src, rows));
+    FY_TRY(llm_join_check(l, "fy_llm_slot_join", slots, n, rows.data(), min_len, max_len));
+    const int R = (int)src.size();
+    HIP_TRY(hipMemcpyAsync(l->row_src, src.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(stream_wait(st));                        // src dies with this frame
+    FY_TRY(llm_join_save(l, st));
+    hipLaunchKernelGGL(embed_rows_k, dim3(R), dim3(256), 0, st, l->row_src, l->embed_tokens, l->embed_tokens_f32, l->speech_emb, l->h, l->cfg.hidden);
+    return llm_join_rows(l, slots, n, rows.data(), min_len, max_len, st);
+}
+
+extern "C" int fy_llm_slot_join_embeds(fy_llm* l, const int32_t* slots, int32_t n, const void* embeds, int32_t dtype, const int32_t* n_rows,
+                                       const int32_t* min_len, const int32_t* max_len, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(l && slots && embeds && n_rows && min_len && max_len && (dtype == 0 || dtype == 1), FY_ERR_ARG,
+             "fy_llm_slot_join_embeds: bad argument (dtype 0 = fp32, 1 = bf16)");
+    FY_TRY(llm_join_check(l, "fy_llm_slot_join_embeds", slots, n, n_rows, min_len, max_len));
+    const int H = l->cfg.hidden;
+    long R = 0;
+    for (int j = 0; j < n; ++j) R += n_rows[j];
+    FY_TRY(llm_join_save(l, st));
+    const unsigned grid = (unsigned)std::min<long>(2048, (R * H + 255) / 256);
+    if (dtype == 0) hipLaunchKernelGGL(copy_rows_k, dim3(grid), dim3(256), 0, st, (const float*)embeds, l->h, R * H);
+    else hipLaunchKernelGGL(rows_from_bf16_k, dim3(grid), dim3(256), 0, st, (const bf16_t*)embeds, l->h, R * H);
+    HIP_TRY(hipGetLastError());
+    return llm_join_rows(l, slots, n, n_rows, min_len, max_len, st);
+}
+
+// fy_llm_step in a slot session: rows 0 .. highest running slot; results indexed by slot (max_batch entries)
+static int llm_step_slots(fy_llm* l, int n_steps, int32_t* out_ids, int out_ld, int32_t* out_n, int32_t* raw_n, int32_t* finished, hipStream_t st) {
+    const int mb = l->max_batch, B = llm_slot_rows(l);
+    std::vector<int> done(mb, 0), used(mb, 0);
+    const std::vector<int> before = l->slot_state;
+    if (B > 0) {
+        const bool persistent = l->dec && l->decode_mode == 1 && B <= 8;
+        const bool persistent32 = !persistent && l->dec32 && (l->decode_mode == 1 || l->decode_mode == 2) && B <= 32;
+        unsigned dec_status = 0;
+        auto read_done = [&]() -> int {
+            HIP_TRY(hipMemcpyAsync(done.data(), l->st + 3 * mb, mb * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (l->sampler == 1) HIP_TRY(hipMemcpyAsync(used.data(), l->st + 7 * mb, mb * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (persistent) FY_TRY(decode_status(l->dec, &dec_status, st));
+            if (persistent32) FY_TRY(decode32_status(l->dec32, &dec_status, st));
+            HIP_TRY(stream_wait(st));
+            if (dec_status != 0) {
+                l->slots_open = false;           // the session is void: no further steps are launched on it
+                FY_CHECK(false, FY_ERR_STATE, "fy_llm_step: the decode kernel's grid hand-off timed out (its workgroups were not all resident: "
+                         "another persistent grid on the device, or a CU-masked stream?); call fy_llm_set_decode_mode(handle, 0) or set "
+                         "FY_LLM_PERSISTENT=0 to use the multi-launch path, then open the slot session again");
+            }
+            return FY_OK;
+        };
+        if (l->gv32 && l->ssq_rpad != 32 * cdiv(B, 32)) {        // the row count crossed a multiple of 32: ssq moves to the new stride
+            l->ssq_rpad = 32 * cdiv(B, 32);
+            hipLaunchKernelGGL(slot_restore_k, dim3(B), dim3(256), 0, st, l->h, l->h, l->st, mb, l->cfg.hidden, llm_next_img(l, l->ssq_rpad));
+        }
+        l->B = B;
+        for (int k = 0; k < n_steps; ++k) {
+            FY_TRY(llm_token_step(l, B, persistent, persistent32, out_ids, out_ld, -1, st));
+            ++l->slot_steps;
+            if ((k & 7) == 7 && k + 1 < n_steps) {
+                FY_TRY(read_done());
+                bool all = true;
+                for (int b = 0; b < B; ++b) all = all && (l->slot_state[b] != 1 || done[b]);
+                if (all) break;
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(out_n, l->st + 2 * mb, mb * sizeof(int), hipMemcpyDeviceToDevice, st));
+        if (raw_n) HIP_TRY(hipMemcpyAsync(raw_n, l->st + 1 * mb, mb * sizeof(int), hipMemcpyDeviceToDevice, st));
+        FY_TRY(read_done());
+        for (int b = 0; b < mb; ++b) if (l->slot_state[b] == 1 && done[b]) l->slot_state[b] = 2;
+    } else {
+        HIP_TRY(hipMemcpyAsync(out_n, l->st + 2 * mb, mb * sizeof(int), hipMemcpyDeviceToDevice, st));
+        if (raw_n) HIP_TRY(hipMemcpyAsync(raw_n, l->st + 1 * mb, mb * sizeof(int), hipMemcpyDeviceToDevice, st));
+    }
+    if (finished) for (int b = 0; b < mb; ++b) finished[b] = l->slot_state[b] != 1;
+    if (l->sampler == 1)                     // reported once, by the step that saw the slot end; the other slots go on
+        for (int b = 0; b < mb; ++b) {
+            if (before[b] != 1) continue;
+            FY_CHECK(done[b] != 2, FY_ERR_STATE, "sampling reaches max_trials 100 and still get eos when ignore_eos is True (slot %d)", b);
+            FY_CHECK(used[b] <= l->n_uniforms, FY_ERR_ARG, "fy_llm_step: slot %d needed %d uniforms, %ld were supplied", b, used[b], l->n_uniforms);
+        }
     return FY_OK;
 }
 
@@ -1098,6 +1386,7 @@ extern "C" int fy_llm_set_sampler(fy_llm* l, int32_t kind, const float* uniforms
 
 extern "C" int fy_llm_logp(fy_llm* l, int32_t step, float* dst, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(!(l && l->slots_open), FY_ERR_STATE, "fy_llm_logp: no log-probabilities are kept in a slot session (they belong to fy_llm_generate / fy_llm_begin)");
     FY_CHECK(l && dst && step >= 0 && step < FY_LLM_KEEP_LOGP && l->B > 0, FY_ERR_ARG, "fy_llm_logp: bad argument or no call made yet");
     const int NS = l->n_speech();
     for (int b = 0; b < l->B; ++b)

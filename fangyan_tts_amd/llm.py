@@ -4,7 +4,8 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence
+from collections import deque
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -20,6 +21,42 @@ def _cfg_struct(cfg: LlmCfg, weight_planes: int = 0) -> _lib.LlmConfig:
     c.inter, c.vocab, c.speech_tokens, c.rms_eps, c.rope_theta = cfg.inter, cfg.vocab, cfg.speech_tokens, cfg.rms_eps, cfg.rope_theta
     c.weight_planes = weight_planes
     return c
+
+
+def _fill_slots(free: Sequence[int], pending: deque) -> List[Tuple[int, int]]:
+    """The slot policy: requests in arrival order into the lowest free slots -> [(request, slot)]."""
+    return [(pending.popleft(), s) for s in sorted(free)[: len(pending)]]
+
+
+def plan_slots(raw_lengths: Sequence[int], n_slots: int, steps_per_poll: int = 8):
+    """The schedule `LlmEngine.generate_continuous` runs when request r emits exactly raw_lengths[r] tokens (a forced length,
+    min_len == max_len): a pure function of the lengths, no GPU.  Requests enter the lowest free slots in arrival order; the join
+    emits a request's first token, so it needs raw_lengths[r] - 1 token steps; every poll runs `steps_per_poll` token steps while
+    any slot is occupied, then the slots whose request has ended are released and refilled.
+    -> (token_steps, joins): the number of token steps issued, and [(token steps issued before the join, [(request, slot), ...])]."""
+    assert n_slots >= 1 and steps_per_poll >= 1 and all(int(n) >= 1 for n in raw_lengths)
+    pending = deque(range(len(raw_lengths)))
+    left: Dict[int, int] = {}                 # slot -> token steps its request still needs
+    t, joins = 0, []
+    while pending or left:
+        batch = _fill_slots([s for s in range(n_slots) if s not in left], pending)
+        if batch:
+            joins.append((t, batch))
+            for r, s in batch:
+                left[s] = int(raw_lengths[r]) - 1
+        t += steps_per_poll
+        left = {s: n - steps_per_poll for s, n in left.items() if n > steps_per_poll}
+    return t, joins
+
+
+def grouped_steps(raw_lengths: Sequence[int], n_slots: int, steps_per_poll: int = 8) -> int:
+    """Token steps of the schedule without slots: arrival-order groups of n_slots, each run to its longest request (its first
+    token comes from the prefill), the stop flags looked at every steps_per_poll steps."""
+    t = 0
+    for g in range(0, len(raw_lengths), n_slots):
+        need = max(int(n) for n in raw_lengths[g: g + n_slots]) - 1
+        t += max(1, -(-need // steps_per_poll)) * steps_per_poll
+    return t
 
 
 class LlmEngine:
@@ -80,7 +117,8 @@ class LlmEngine:
         except Exception:
             pass
 
-    def _pack(self, text, prompt_text, prompt_speech, min_len, max_len, min_ratio, max_ratio):
+    @staticmethod
+    def _pack_ids(text, prompt_text, prompt_speech, min_len, max_len, min_ratio, max_ratio):
         B = len(text)
         ids, n_all, ps, n_ps = [], [], [], []
         for b in range(B):
@@ -90,13 +128,17 @@ class LlmEngine:
             n_ps.append(len(prompt_speech[b]))
         mn = [int(len(text[b]) * min_ratio) for b in range(B)] if min_len is None else list(min_len)
         mx = [int(len(text[b]) * max_ratio) for b in range(B)] if max_len is None else list(max_len)
+        return (_lib.int_array(ids), _lib.int_array(n_all), _lib.int_array(ps or [0]), _lib.int_array(n_ps), _lib.int_array(mn),
+                _lib.int_array(mx)), mx
+
+    def _pack(self, text, prompt_text, prompt_speech, min_len, max_len, min_ratio, max_ratio):
+        B = len(text)
+        arrays, mx = self._pack_ids(text, prompt_text, prompt_speech, min_len, max_len, min_ratio, max_ratio)
         out_ld = max(mx)
         out = torch.zeros(B, out_ld, dtype=torch.int32, device=self.device)
         out_n = torch.zeros(B, dtype=torch.int32, device=self.device)
         raw_n = torch.zeros(B, dtype=torch.int32, device=self.device)
-        args = (_lib.int_array(ids), _lib.int_array(n_all), _lib.int_array(ps or [0]), _lib.int_array(n_ps), _lib.int_array(mn),
-                _lib.int_array(mx), B, out.data_ptr(), out_ld)
-        return args, out, out_n, raw_n
+        return (*arrays, B, out.data_ptr(), out_ld), out, out_n, raw_n
 
     def generate(self, text: Sequence[Sequence[int]], prompt_text: Sequence[Sequence[int]],
                  prompt_speech: Sequence[Sequence[int]], min_len: Optional[Sequence[int]] = None,
@@ -132,8 +174,82 @@ class LlmEngine:
         self._gen = (out, out_n, raw_n, B)
         return out, out_n, raw_n
 
+    # ---- decode slots: sequences join and leave between token steps (fy_llm_slots_open ...) ----
+    def open_slots(self, out_ld: Optional[int] = None):
+        """Start a slot session: all `max_batch` slots free.  Returns (out_ids (max_batch, out_ld), out_n, raw_n), CUDA int32,
+        indexed by slot; they fill up as `join` and `step` are called.  out_ld defaults to max_ctx (no sequence can emit more)."""
+        out_ld = int(out_ld or self.max_ctx)
+        out = torch.zeros(self.max_batch, out_ld, dtype=torch.int32, device=self.device)
+        out_n = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+        raw_n = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+        check(_lib.lib().fy_llm_slots_open(self._h, out.data_ptr(), out_ld, self._stream()))
+        self._gen = (out, out_n, raw_n, self.max_batch)
+        return out, out_n, raw_n
+
+    def join(self, slots: Sequence[int], text, prompt_text, prompt_speech, min_len=None, max_len=None, min_ratio: float = 2,
+             max_ratio: float = 20):
+        """Prefill new sequences (arguments as `begin`) into the free slots `slots` and sample their first tokens; the slots
+        already running are untouched and go on at the next `step`."""
+        arrays, _ = self._pack_ids(text, prompt_text, prompt_speech, min_len, max_len, min_ratio, max_ratio)
+        check(_lib.lib().fy_llm_slot_join(self._h, _lib.int_array(slots), len(slots), *arrays, self._stream()))
+
+    def join_embeds(self, slots: Sequence[int], embeds: Sequence[torch.Tensor], min_len: Sequence[int], max_len: Sequence[int]):
+        """`join` from embedding rows (as `prefill_embeds`): the reference's `add_request(uuid, prompt_embeds, SamplingParams)`."""
+        dt = embeds[0].dtype
+        assert dt in (torch.float32, torch.bfloat16) and all(e.dtype == dt and e.dim() == 2 and e.shape[1] == self.cfg.hidden for e in embeds)
+        rows = torch.cat([e.to(self.device) for e in embeds], dim=0).contiguous()
+        check(_lib.lib().fy_llm_slot_join_embeds(self._h, _lib.int_array(slots), len(slots), rows.data_ptr(), 0 if dt == torch.float32 else 1,
+                                                 _lib.int_array([e.shape[0] for e in embeds]), _lib.int_array(min_len), _lib.int_array(max_len),
+                                                 self._stream()))
+        del rows                                             # the caching allocator keeps it for the stream's queued work
+
+    def release(self, slot: int):
+        """Free a slot, ended or not (a cancelled request)."""
+        check(_lib.lib().fy_llm_slot_release(self._h, int(slot), self._stream()))
+
+    def live(self) -> List[int]:
+        """The occupied slots of the session (running, or ended and not yet released)."""
+        state = (C.c_int32 * self.max_batch)()
+        _lib.lib().fy_llm_slots_live(self._h, state)
+        return [s for s in range(self.max_batch) if state[s]]
+
+    @property
+    def slot_steps(self) -> int:
+        """Token steps launched since `open_slots`."""
+        return int(_lib.lib().fy_llm_slots_steps(self._h))
+
+    def generate_continuous(self, text, prompt_text, prompt_speech, min_len: Optional[Sequence[int]] = None,
+                            max_len: Optional[Sequence[int]] = None, steps_per_poll: int = 8, min_ratio: float = 2, max_ratio: float = 20):
+        """Any number of requests (more than max_batch too) through the slots, in arrival order: join into the lowest free slots,
+        `steps_per_poll` token steps, collect and release the slots that ended, refill - the schedule `plan_slots` computes.
+        -> (ids, raw_n): per request the emitted ids (silent-token filter applied, as `generate`) and the count before the filter."""
+        N = len(text)
+        mn = [int(len(t) * min_ratio) for t in text] if min_len is None else list(min_len)
+        mx = [int(len(t) * max_ratio) for t in text] if max_len is None else list(max_len)
+        out, out_n, raw_n = self.open_slots(max(mx))
+        pending, occupied = deque(range(N)), {}
+        ids: List[Optional[List[int]]] = [None] * N
+        raw = [0] * N
+        while pending or occupied:
+            batch = _fill_slots([s for s in range(self.max_batch) if s not in occupied], pending)
+            if batch:
+                rs = [r for r, _ in batch]
+                self.join([s for _, s in batch], [text[r] for r in rs], [prompt_text[r] for r in rs], [prompt_speech[r] for r in rs],
+                          min_len=[mn[r] for r in rs], max_len=[mx[r] for r in rs])
+                occupied.update({s: r for r, s in batch})
+            n, fin = self.step(steps_per_poll)
+            ended = [s for s in occupied if fin[s]]
+            if ended:
+                host, rn = out.cpu(), raw_n.cpu().tolist()
+                for s in ended:
+                    r = occupied.pop(s)
+                    ids[r], raw[r] = host[s, : n[s]].tolist(), rn[s]
+                    self.release(s)
+        return ids, raw
+
     def step(self, n_steps: int):
-        """Up to `n_steps` more tokens for the sequences still running -> (tokens kept so far per sequence, finished flags)."""
+        """Up to `n_steps` more tokens for the sequences still running -> (tokens kept so far per sequence, finished flags).
+        In a slot session both lists have max_batch entries, indexed by slot (free slots: 0, True)."""
         out, out_n, raw_n, B = self._gen
         fin = (C.c_int32 * B)()
         check(_lib.lib().fy_llm_step(self._h, int(n_steps), out.data_ptr(), out.shape[1], out_n.data_ptr(), raw_n.data_ptr(), fin,

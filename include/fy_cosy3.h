@@ -237,12 +237,44 @@ int fy_llm_prefill(fy_llm* l, const void* embeds, int32_t dtype, const int32_t* 
                    int32_t B, int32_t* out_ids, int32_t out_ld, void* stream);
 int fy_llm_step(fy_llm* l, int32_t n_steps, int32_t* out_ids, int32_t out_ld, int32_t* out_n, int32_t* raw_n,
                 int32_t* finished, void* stream);
-/* Sampler used by the following fy_llm_generate calls.  kind 0: the greedy rule above.  kind 1: the reference's default,
+/* ---- decode slots: sequences join and leave the batch between token steps (the engine-level shape of the reference's vLLM
+ * hand-off, llm.py:482-510: add_request at any time, then step() per token; its gRPC server calls tts() from a thread pool, so
+ * requests arrive while others decode).  A slot is one of the handle's max_batch sequence places: it owns its KV cache, position,
+ * counts, silent-token run, sampling window, row of the sampler's uniforms and row of out_ids.  The ids a sequence emits depend
+ * only on its own inputs and uniforms: not on the slot, on when it joined, on who else is live, on the decode mode or on the number
+ * of weight planes.  Calls of a session are serial on one stream.
+ * fy_llm_slots_open: starts a session; every slot is free, a fy_llm_begin generation in progress is void.  out_ids: device
+ * (max_batch, out_ld) int32, row = slot.  fy_llm_begin / fy_llm_prefill / fy_llm_generate close the session.                       */
+int fy_llm_slots_open(fy_llm* l, int32_t* out_ids, int32_t out_ld, void* stream);
+/* Prefill n new sequences into the free slots `slots` (host int32[n], distinct) and sample the first token of each; the other
+ * slots keep their state bit for bit.  Inputs packed over the n sequences as in fy_llm_begin.  The slot's uniforms row is consumed
+ * from its start.  FY_ERR_STATE: no session, slot live; FY_ERR_ARG: slot out of range or named twice, lengths, more rows than the
+ * prefill workspace, more positions than max_ctx - all before any device work, the session stays as it was.                       */
+int fy_llm_slot_join(fy_llm* l, const int32_t* slots, int32_t n, const int32_t* text_ids, const int32_t* n_text_all,
+                     const int32_t* prompt_speech, const int32_t* n_prompt_speech, const int32_t* min_len, const int32_t* max_len,
+                     void* stream);
+/* The same from embedding rows, packed as in fy_llm_prefill: `add_request(uuid, prompt_embeds, SamplingParams)`.                  */
+int fy_llm_slot_join_embeds(fy_llm* l, const int32_t* slots, int32_t n, const void* embeds, int32_t dtype, const int32_t* n_rows,
+                            const int32_t* min_len, const int32_t* max_len, void* stream);
+/* In a session fy_llm_step advances every running slot by up to n_steps tokens (each slot's own max_len bounds it); out_ids /
+ * out_ld as given to fy_llm_slots_open; out_n, raw_n (device) and finished (host) have max_batch entries indexed by slot, free
+ * slots report 0 / 0 / 1.  The step runs highest running slot + 1 rows; with no running slot it launches nothing.  When the
+ * sampler gives up on a slot (> 100 retries) the call returns FY_ERR_STATE with the reference's message and the slot number once,
+ * that slot has ended, and the session goes on for the others.  fy_llm_logp returns FY_ERR_STATE in a session.
+ * fy_llm_slot_release frees a slot, ended or not (a cancelled request); the next join into it meets nothing of the previous
+ * occupant.  fy_llm_slots_live: the number of occupied slots; state (nullable, host int32[max_batch]): 0 free, 1 running,
+ * 2 ended and not yet released.  fy_llm_slots_steps: token steps launched since fy_llm_slots_open.                                */
+int fy_llm_slot_release(fy_llm* l, int32_t slot, void* stream);
+int fy_llm_slots_live(const fy_llm* l, int32_t* state);
+int64_t fy_llm_slots_steps(const fy_llm* l);
+/* Sampler used by the following fy_llm_generate, fy_llm_begin / fy_llm_prefill + fy_llm_step and slot-session calls.
+ * kind 0: the greedy rule above.  kind 1: the reference's default,
  * repetition-aware sampling (utils/common.py:137-166 `ras_sampling` with top_p, top_k, win_size, tau_r = 0.8, 25, 10, 0.1 in
  * cosyvoice3.yaml) inside the ignore_eos retry loop of `sampling_ids` (llm/llm.py:149-164; > 100 retries -> FY_ERR_STATE with
  * the reference's message).  torch.multinomial's draws are replaced by the inverse CDF at caller-supplied uniforms:
- * `uniforms` is device fp32 (max_batch, n_uniforms), borrowed until the next call; sequence b consumes its row from the
- * start of every fy_llm_generate call, one value per multinomial the reference would draw.                               */
+ * `uniforms` is device fp32 (max_batch, n_uniforms), borrowed until the next call; sequence (slot) b consumes its row from the
+ * start at every fy_llm_generate / fy_llm_begin / fy_llm_prefill call and at every join into slot b, one value per multinomial the
+ * reference would draw.                                                                                                   */
 int fy_llm_set_sampler(fy_llm* l, int32_t kind, const float* uniforms, int64_t n_uniforms, int32_t top_k, float top_p,
                        int32_t win_size, float tau_r);
 /* How fy_llm_step runs a token step (Qwen2Encoder.forward_one_step + llm_decoder, llm/llm.py:246-258, 518).
