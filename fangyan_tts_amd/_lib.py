@@ -99,6 +99,13 @@ def _declare(L):
     L.fy_flow_infer.argtypes = [vp, vp, i32, i32p, vp, i32, i32p, f32p, i32, i32p, f32p, f32p, i32, i32, f32p, i32, u32, vp]
     L.fy_flow_stream_reset.argtypes = [vp]
     L.fy_flow_stream_rows.argtypes = [vp]
+    L.fy_flow_streams_open.argtypes = [vp, i32, i32]
+    L.fy_flow_streams_close.argtypes = [vp]
+    L.fy_flow_streams_bytes.argtypes = [vp]
+    L.fy_flow_streams_bytes.restype = C.c_int64
+    L.fy_flow_stream_slot_reset.argtypes = [vp, i32]
+    L.fy_flow_stream_slot_rows.argtypes = [vp, i32]
+    L.fy_flow_infer_streams.argtypes = [vp, i32p, i32, vp, i32, i32p, vp, i32, i32p, f32p, i32, i32p, f32p, f32p, i32, f32p, i32, u32, vp]
     L.fy_dit_estimator.argtypes = [vp, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, u32, vp]
     L.fy_llm_default_config.argtypes = [C.POINTER(LlmConfig)]
     L.fy_llm_default_config.restype = None

@@ -123,6 +123,7 @@ class CosyVoice3Model:
         fb = max_batch * self.flow_group
         self.flow = FlowEngine(flow_weights, cfg.flow, max_batch=fb, max_frames=max_frames, device=self.device)
         self.hift = HiftEngine(hift_weights, cfg.hift, max_batch=fb, max_frames=2 * max_tokens, device=self.device)
+        self._hift_weights = hift_weights     # tts_stream_batch builds one small vocoder handle per stream slot on first use
         # The reference lets several threads enter tts() on one model object (a gRPC pool, runtime/python/grpc/server.py:68-69;
         # per-call state keyed by uuid, cli/model.py:330-333).  An engine handle is single-threaded, so concurrent calls each
         # take a LANE - an own (LM, flow, vocoder) handle set and stream; `concurrency` lanes exist (the reference's
@@ -743,6 +744,89 @@ class CosyVoice3Model:
                 ahead.stop()                                # (an abandoned generator: the LM thread ends after its current slice)
                 if mode_was is not None:
                     ln.llm.set_decode_mode(mode_was)
+            self._release_lane(ln)
+
+    # ------------------------------------------------------------------ K stream=True utterances on ONE lane
+    @torch.inference_mode()
+    def tts_stream_batch(self, inputs: Sequence[Dict[str, torch.Tensor]]):
+        """K stream=True generations through one lane: one LM slot session (`open_slots / join / step / release`, stepped
+        `token_hop_len` tokens per poll) and one flow stream-slot session.  Every poll runs ONE `FlowEngine.inference_streams` call
+        for all streams whose next hop + look-ahead tokens exist, then each such stream's incremental vocoder (a HiftEngine per
+        stream slot), and yields (index, {'tts_speech': (1, S) on CPU}).  A stream whose LM has ended gets the reference's final pass
+        (finalize=True, no chunk mask; the plain `inference`, batched over the streams that end in the same poll).  Each stream's
+        chunks are those `tts(stream=True)` yields for it alone: the chunk boundaries depend on its token count only
+        (`flow.stream_chunk_plan`) and the LM's ids on its own inputs.  Under the "ras" sampler stream i draws from row i of the
+        call's uniforms."""
+        K = len(inputs)
+        assert 1 <= K <= self.max_batch
+        z = torch.zeros(1, 0, dtype=torch.int32)
+        text = [d["text"].reshape(-1).tolist() for d in inputs]
+        ptext = [d.get("prompt_text", z).reshape(-1).tolist() for d in inputs]
+        pspeech = [d.get("llm_prompt_speech_token", z).reshape(-1).tolist() for d in inputs]
+        self._check_capacity(inputs, None)
+        ptok, n_fp, pfeat, n_pf, emb = self._prompt_tensors(inputs)
+        look, hop, up = self.cfg.flow.pre_lookahead, self.token_hop_len, self.cfg.hift.upsample_total
+        pads = [-(-p // hop) * hop - p for p in n_fp]
+        ln = self._acquire_lane()
+        opened = False
+        try:
+            hifts = ln.__dict__.setdefault("stream_hifts", [ln.hift])
+            while len(hifts) < K:
+                hifts.append(HiftEngine(self._hift_weights, self.cfg.hift, max_batch=1, max_frames=2 * self.max_tokens, device=self.device))
+            with self._lane_stream(ln):
+                self._arm_lane_sampler(ln, self._next_batch_ids(), K)
+                out, _, _ = ln.llm.open_slots(self.max_tokens)
+                ln.llm.join(list(range(K)), text, ptext, pspeech)
+                ln.flow.open_streams(K, 2 * (self.max_tokens + self.max_prompt_tokens))
+                opened = True
+                for i in range(K):
+                    ln.flow.stream_slot_reset(i)
+                    hifts[i].stream_reset()
+            offset, speech, mel_all, live = [0] * K, [0] * K, [None] * K, set(range(K))
+
+            def vocode(i, mel, n_in, finalize):
+                valid = 2 * (n_in if finalize else n_in - look)
+                mel = mel[:, :, 2 * offset[i]: valid]
+                mel_all[i] = mel if mel_all[i] is None else torch.cat([mel_all[i], mel], dim=2)
+                wav, _ = hifts[i].inference(mel_all[i].contiguous(), self.rand_ini, self.sine_noise, finalize=finalize, flags=self.hift_flags,
+                                            incremental=True)
+                end = up * (mel_all[i].shape[2] if finalize else mel_all[i].shape[2] - 8)
+                res = wav[:, speech[i]:end].cpu()
+                speech[i] = end
+                return res
+
+            while live:
+                results = []
+                with self._lane_stream(ln):
+                    n, fin = ln.llm.step(hop)
+                    need = {i: offset[i] + (hop + pads[i] if offset[i] == 0 else hop) + look for i in live}
+                    ready = sorted(i for i in live if n[i] >= need[i])
+                    ended = sorted(i for i in live if n[i] < need[i] and fin[i])
+                    if ready:
+                        ix = torch.tensor(ready, device=self.device)
+                        mel = ln.flow.inference_streams(ready, out[ix, : max(need[i] for i in ready)], [need[i] for i in ready], ptok[ix],
+                                                        [n_fp[i] for i in ready], pfeat[ix], [n_pf[i] for i in ready], emb[ix], self.rand_noise,
+                                                        flags=self.flow_flags)
+                        for j, i in enumerate(ready):
+                            results.append((i, vocode(i, mel[j: j + 1], need[i], False)))
+                            offset[i] = need[i] - look
+                    for g in range(0, len(ended), ln.flow.max_batch):
+                        grp = ended[g: g + ln.flow.max_batch]
+                        if min(n[i] for i in grp) < 1:
+                            raise RuntimeError("the language model emitted no speech token for an utterance")
+                        ix = torch.tensor(grp, device=self.device)
+                        mel = ln.flow.inference(out[ix, : max(n[i] for i in grp)].contiguous(), [n[i] for i in grp], ptok[ix], [n_fp[i] for i in grp],
+                                                pfeat[ix], [n_pf[i] for i in grp], emb[ix], self.rand_noise, flags=self.flow_flags)
+                        for j, i in enumerate(grp):
+                            results.append((i, vocode(i, mel[j: j + 1], n[i], True)))
+                            ln.llm.release(i)
+                            ln.flow.stream_slot_reset(i)
+                            live.discard(i)
+                for i, wav in results:
+                    yield i, {"tts_speech": wav}
+        finally:
+            if opened:
+                ln.flow.close_streams()
             self._release_lane(ln)
 
     # ------------------------------------------------------------------ reference-shaped path

@@ -11,6 +11,13 @@ int dit_attention(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, 
 // the default kernel behind dit_attention (attn_dit.hip): row t of sequence s at row s * seq_rows + t * row_step
 int dit_attention2(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, int seq_rows, int row_step);
 
+// The per-sequence form of the same kernel (the flow decoder's stream slots): sequence s has its own first query row, length, base
+// row in qkv and first output row; frame t of it is row in_row + t * row_step of qkv, and query t >= q_begin is written to row
+// out_row + (t - q_begin) * row_step of out.  Tmax: the longest sequence (sizes the grid).  A query's result is what dit_attention
+// gives for the same row and keys.
+struct DitSeqTab { int q_begin, len, in_row, out_row; };
+int dit_attention_tab(const bf16_t* qkv, bf16_t* out, const DitSeqTab* tab, int nseq, int Tmax, int H, int chunk, int row_step, hipStream_t st);
+
 // The split-operand form (fp32-class flow decoder): q, k, v and the output as x = hi + lo, two bf16 planes each, same layouts;
 // three MFMAs per product keep the hi x hi, hi x lo and lo x hi terms, softmax in fp32.
 int dit_attention_split(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* out_hi, bf16_t* out_lo, const int* seq_len, int nseq, int Tmax, int H, int chunk,

@@ -65,9 +65,13 @@ void at2_set_stamps(unsigned long long* p) { hipMemcpyToSymbol(HIP_SYMBOL(at2_st
 #else
 #define AT2_STAMP(i) do { } while (0)
 #endif
-template <int NW, bool ONES>
+// TAB (the flow decoder's stream slots): seq_len is a table of DitSeqTab, one per sequence - its first query row, its length, the row of
+// its frame 0 in qkv and the output row of its first query - instead of one q_begin and the affine s * seq_rows mapping; row_step
+// holds for both.  Streams at different lengths and chunk indices then share one launch: the grid is sized for the longest, and a
+// workgroup without queries leaves at once.  The key loop, the masks and the softmax are the same code.
+template <int NW, bool ONES, bool TAB = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void dit_attention2_k(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, const int* __restrict__ seq_len, int Tmax, int H,
-                                                        int chunk, float scale_log2, int q_begin, int seq_rows, int row_step) {
+                                                        int chunk, float scale_log2, int q_begin_arg, int seq_rows, int row_step) {
     constexpr int NQ = 2, NT = NW * 64, NLD = 512 / NT;                               // blocks per wave; threads; 16-byte chunks of a 64-key tile per thread
     constexpr int KSZ = 64 * AT_KP, VSZ = 64 * AT_VP, QW = NQ * 32, QB = NW * QW;     // queries per wave, per workgroup
     static_assert(NW == 4 || NW == 8, "four or eight waves");
@@ -76,12 +80,20 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     bf16_t* const Vbuf = at2_smem + 3 * KSZ;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int s = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * QB;
-    const int len = seq_len[s];
+    int len, q_begin;
+    long in_row = 0, out_row = 0;
+    if constexpr (TAB) {
+        const int4 t = reinterpret_cast<const int4*>(seq_len)[s];
+        q_begin = t.x; len = t.y; in_row = t.z; out_row = t.w;
+    } else {
+        len = seq_len[s];
+        q_begin = q_begin_arg;
+    }
     if (q0 >= len || q0 + QB <= q_begin) return;
     AT2_STAMP(0);
     const int ld = 3 * H * AT_D;
     const long ldr = (long)ld * row_step;
-    const bf16_t* base = qkv + (long)s * seq_rows * ld;
+    const bf16_t* base = qkv + (TAB ? in_row : (long)s * seq_rows) * ld;
     const int lr = lane & 31, hf = lane >> 5;
     const int qrow0 = q0 + wid * QW + lr;                    // this lane's queries: qrow0 + 32 q
     frag_ab qf[NQ][4];                                       // B[k = 16ks + 8hf + j][col = query]
@@ -339,7 +351,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const int row = ps_ * 8 + (lane >> 3), qrow = q0 + wid * QW + 32 * q + row;
             const uint4 v = *reinterpret_cast<const uint4*>(orow + row * AT_KP + (lane & 7) * 8);
             if (qrow < len && qrow >= q_begin)
-                *reinterpret_cast<uint4*>(out + ((long)s * seq_rows + (long)qrow * row_step) * (H * AT_D) + h * AT_D + (lane & 7) * 8) = v;
+                *reinterpret_cast<uint4*>(out + (TAB ? out_row + (long)(qrow - q_begin) * row_step : (long)s * seq_rows + (long)qrow * row_step) * (H * AT_D) + h * AT_D + (lane & 7) * 8) = v;
         }
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -351,6 +363,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
 int dit_attention2(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, int seq_rows, int row_step) {
     const float sl2 = 0.125f * 1.4426950408889634f;
+    ProfScope prof("dit_attention", 0.0, st);
     // 64 queries per wave.  Up to 256 frames: four waves per workgroup; longer sequences: eight (512 queries, one workgroup per CU) -
     // at the benchmark's 400 frames a (sequence, head)'s keys and values are then fetched once, not once per 256 queries
     // (52 MB instead of 78 per call: at 16 x 400 x 16 heads the call moves as long as it computes)
@@ -365,6 +378,20 @@ int dit_attention2(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq,
         dim3 grid(g8, H, nseq);
         hipLaunchKernelGGL((dit_attention2_k<8, true>), grid, dim3(512), 0, st, qkv, out, seq_len, Tmax, H, chunk, sl2, q_begin, seq_rows, row_step);
     }
+    HIP_TRY(hipGetLastError());
+    return FY_OK;
+}
+
+int dit_attention_tab(const bf16_t* qkv, bf16_t* out, const DitSeqTab* tab, int nseq, int Tmax, int H, int chunk, int row_step, hipStream_t st) {
+    FY_CHECK(qkv && out && tab && nseq >= 1 && Tmax >= 1 && H >= 1 && row_step >= 1, FY_ERR_ARG, "dit_attention_tab: bad arguments");
+    const float sl2 = 0.125f * 1.4426950408889634f;
+    ProfScope prof("dit_attention", 0.0, st);
+    // the tiling rule of dit_attention2, on the longest sequence
+    const int nqb = cdiv(Tmax, 32), g8 = cdiv(nqb, 16), g4 = cdiv(nqb, 8);
+    const bool four = Tmax <= 256 || 10 * nqb * (2 * g8 - g4) > g4 * g8 * 16;
+    const int* t = reinterpret_cast<const int*>(tab);
+    if (four) hipLaunchKernelGGL((dit_attention2_k<4, true, true>), dim3(g4, H, nseq), dim3(256), 0, st, qkv, out, t, Tmax, H, chunk, sl2, 0, 0, row_step);
+    else hipLaunchKernelGGL((dit_attention2_k<8, true, true>), dim3(g8, H, nseq), dim3(512), 0, st, qkv, out, t, Tmax, H, chunk, sl2, 0, 0, row_step);
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }

@@ -12,6 +12,7 @@
 #include "gemm.h"
 #include "runtime.h"
 #include <math.h>
+#include <type_traits>
 
 struct FlowBlockW {
     bf16_t *wqkv, *wo, *w1, *w2, *wmod;
@@ -61,8 +62,33 @@ struct fy_flow {
     float* inc_x = nullptr;
     int inc_T = 0;
     int inc_np = -1, inc_npf = -1, inc_ntok = -1;       // the stream's prompt tokens / prompt frames / tokens at the last kept call (a cheap check that a call extends it)
-    ~fy_flow() { conv_free(pre1); conv_free(pre2); conv_free(pos1); conv_free(pos2); }
+    struct FlowStreams* ss = nullptr;                   // the stream-slot session (fy_flow_streams_open), or none
+    ~fy_flow();
 };
+
+// Stream slots (fy_flow_streams_open): the incremental caches of n_slots concurrent stream=True utterances and the work buffers of
+// the call that advances any subset of them by a chunk each (fy_flow_infer_streams).  The caches hold, per slot, what inc_qkv / inc_x
+// hold for the single stream, at a pitch of cap frames; a (step, block) slice spans all slots so that one attention launch reaches
+// every listed stream's keys.
+struct FlowStreams {
+    int n_slots = 0, cap = 0, ncap = 0;      // cap: mel rows per slot (even); ncap: tokens per slot (cap / 2 + look-ahead)
+    size_t bytes = 0;
+    bf16_t* qkv = nullptr;                   // [n_steps][depth][n_slots][2 cap][3 inner]: frame t of sequence s (0 conditional, 1 CFG) of a slot at row 2 t + s
+    float* xs = nullptr;                     // [n_steps + 1][n_slots][cap][mel]: the ODE state at every step
+    // one call's inputs and activations.  Front (input projection, position convs): sequence 2 i + s of listed stream i at rows
+    // (2 i + s) Tp + t, Tp = the call's longest stream, as in dit_forward; blocks: the NEW rows of all listed streams compact,
+    // [stream][frame][sequence] - c1 is the residual stream there
+    int* tab = nullptr;                      // atab [2 n_slots] DitSeqTab | stab [n_slots][4] (slot, T0, T, first compact row) | seq_len [2 n_slots] | blen [5][n_slots]
+    int4* rows = nullptr;                    // per compact row: (front row, cache row inside a slice, frame, slot)
+    int* tok_all = nullptr;
+    float *emb = nullptr, *pre_a = nullptr, *mu_tok = nullptr, *spks = nullptr, *mu = nullptr, *cond = nullptr, *h = nullptr, *c1 = nullptr, *qf = nullptr, *v = nullptr;
+    bf16_t *a_in = nullptr, *xn = nullptr, *ao = nullptr, *ff = nullptr;
+    std::vector<void*> ptrs;
+    struct Slot { int T = 0, np = -1, npf = -1, ntok = -1; };      // rows kept; prompt tokens / prompt frames / tokens at the last kept call
+    std::vector<Slot> slot;
+    ~FlowStreams() { for (void* p : ptrs) (void)hipFree(p); }
+};
+fy_flow::~fy_flow() { conv_free(pre1); conv_free(pre2); conv_free(pos1); conv_free(pos2); delete ss; }
 
 extern "C" void fy_flow_default_config(fy_flow_config* c) {
     memset(c, 0, sizeof(*c));
@@ -207,6 +233,10 @@ __global__ __launch_bounds__(256) void ln_mod_k(const float* __restrict__ h, con
 }
 
 // CFG mix and Euler update, flow_matching.py:114-118
+__device__ __forceinline__ float euler_update(float x, float vc, float vu, float dt, float cfg) {
+    float d = (1.0f + cfg) * vc - cfg * vu;
+    return x + dt * d;
+}
 __global__ void euler_k(float* __restrict__ x, const float* __restrict__ v, const int* __restrict__ T, int Tmax, int C, float dt, float cfg, int t0,
                         int interleaved) {
     int b = blockIdx.y, t = t0 + blockIdx.x, c = threadIdx.x;
@@ -214,9 +244,83 @@ __global__ void euler_k(float* __restrict__ x, const float* __restrict__ v, cons
     // v rows: sequence s at s Tmax + t, or (incremental streaming, batch 1) the two sequences interleaved: 2 t + s
     float vc = interleaved ? v[(2L * t) * C + c] : v[((long)(2 * b) * Tmax + t) * C + c];
     float vu = interleaved ? v[(2L * t + 1) * C + c] : v[((long)(2 * b + 1) * Tmax + t) * C + c];
-    float d = (1.0f + cfg) * vc - cfg * vu;
     long o = ((long)b * Tmax + t) * C + c;
-    x[o] = x[o] + dt * d;
+    x[o] = euler_update(x[o], vc, vu, dt, cfg);
+}
+
+// ---- stream slots: the ragged forms of the kernels above (FlowStreams says where things live) ----------------------------------
+// per compact row: where it came from and where its q | k | v go.  stab: [n][4] = (slot, T0, T, first compact row)
+__global__ void stream_rows_k(const int* __restrict__ stab, int n, int Tp, int cap, int4* __restrict__ rows, int Mn) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= Mn) return;
+    int i = 0;
+    while (i + 1 < n && stab[4 * (i + 1) + 3] <= r) ++i;
+    const int slot = stab[4 * i], T0 = stab[4 * i + 1], j = r - stab[4 * i + 3], t = T0 + (j >> 1), sq = j & 1;
+    rows[r] = make_int4((2 * i + sq) * Tp + t, slot * 2 * cap + 2 * t + sq, t, slot);
+}
+// flow_setup_k over the listed streams: mu and cond of all T frames; the noise is the state at step 0 of the NEW frames only
+__global__ void stream_setup_k(const float* __restrict__ mu_tok, const float* __restrict__ pfeat, long pf_bs, const float* __restrict__ noise, int noise_ld,
+                               const int* __restrict__ stab, const int* __restrict__ pmel, float* __restrict__ mu, float* __restrict__ cond,
+                               float* __restrict__ xs0, int Tp, int Nmax, int cap, int C) {
+    const int i = blockIdx.y, t = blockIdx.x, c = threadIdx.x;
+    const int slot = stab[4 * i], T0 = stab[4 * i + 1], T = stab[4 * i + 2];
+    if (t >= T || c >= C) return;
+    const long o = ((long)i * Tp + t) * C + c;
+    mu[o] = mu_tok[((long)i * Nmax + (t >> 1)) * C + c];
+    cond[o] = t < pmel[i] ? pfeat[(long)i * pf_bs + (long)t * C + c] : 0.f;
+    if (t >= T0) xs0[((long)slot * cap + t) * C + c] = noise[(long)c * noise_ld + t];
+}
+// dit_assemble_k over the listed streams, x from the slots' state of this step
+__global__ void stream_assemble_k(const float* __restrict__ xs, const float* __restrict__ cond, const float* __restrict__ mu, const float* __restrict__ spks,
+                                  const int* __restrict__ stab, bf16_t* __restrict__ a, int Tp, int cap, int C) {
+    const int s = blockIdx.y, t = blockIdx.x, i = s >> 1, cfg = s & 1;
+    const int k = threadIdx.x;               // 0 .. 4C
+    if (k >= 4 * C) return;
+    float v = 0.f;
+    if (t < stab[4 * i + 2]) {
+        const long o = ((long)i * Tp + t) * C;
+        const int part = k / C, c = k % C;
+        if (part == 0) v = xs[((long)stab[4 * i] * cap + t) * C + c];
+        else if (!cfg) v = part == 1 ? cond[o + c] : (part == 2 ? mu[o + c] : spks[(long)i * C + c]);
+    }
+    a[((long)s * Tp + t) * 4 * C + k] = f32_to_bf16(v);
+}
+// the new rows of the residual stream, out of the front layout into the compact one
+__global__ __launch_bounds__(256) void stream_gather_k(const float* __restrict__ h, const int4* __restrict__ rows, float* __restrict__ out, int D) {
+    const int r = blockIdx.x;
+    const float4* src = reinterpret_cast<const float4*>(h + (long)rows[r].x * D);
+    float4* dst = reinterpret_cast<float4*>(out + (long)r * D);
+    for (int k = threadIdx.x; k < D / 4; k += 256) dst[k] = src[k];
+}
+// The qkv product's fp32 sums (+ bias) of the compact rows -> bf16 rows of their slots' (step, block) slice, with the rotary embedding
+// of head 0 of q and of k at the row's own frame: the arithmetic of the products' rotary epilogue (rope_rotate on the sums, then one
+// rounding), which derives a row's position from its index and cannot serve rows of streams at different frames side by side
+__global__ __launch_bounds__(256) void stream_qkv_store_k(const float* __restrict__ qf, const int4* __restrict__ rows, const float2* __restrict__ rope,
+                                                          bf16_t* __restrict__ qkv, int N, int rope_half, int rope_stride) {
+    const int r = blockIdx.x;
+    const int4 rw = rows[r];
+    for (int n = threadIdx.x * 4; n < N; n += 1024) {
+        float4 v = *reinterpret_cast<const float4*>(qf + (long)r * N + n);
+        const int nn = n >= rope_stride ? n - rope_stride : n;
+        if (n < 2 * rope_stride && nn < 2 * rope_half) {
+            const float2* tab = rope + (long)rw.z * rope_half + (nn >> 1);
+            const float2 c0 = tab[0], c1 = tab[1];
+            rope_rotate(v, make_float4(c0.x, c0.y, c1.x, c1.y));
+        }
+        uint2 pk;
+        pk.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);
+        pk.y = (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16);
+        *reinterpret_cast<uint2*>(qkv + (long)rw.y * N + n) = pk;
+    }
+}
+// euler_k over the compact rows: the state of the next step from this step's, in the slots
+__global__ void stream_euler_k(const float* __restrict__ xs, float* __restrict__ xs_next, const float* __restrict__ v, const int4* __restrict__ rows,
+                               int cap, int C, float dt, float cfg) {
+    const int fr = blockIdx.x, c = threadIdx.x;
+    if (c >= C) return;
+    const int4 rw = rows[2 * fr];
+    const long o = ((long)rw.w * cap + rw.z) * C + c;
+    xs_next[o] = euler_update(xs[o], v[(2L * fr) * C + c], v[(2L * fr + 1) * C + c], dt, cfg);
 }
 
 __global__ void silu_k(const float* __restrict__ a, float* __restrict__ o, long n) {
@@ -745,6 +849,34 @@ extern "C" int fy_flow_stream_reset(fy_flow* f) {
     return FY_OK;
 }
 
+// front of a call: speaker projection, token embedding, PreLookahead (upsample_encoder.py:82-103) over B utterances at a pitch of
+// Nmax tokens, into the buffers of the handle or of its stream-slot session
+struct FlowFront { int* tok_all; float *emb, *pre_a, *mu_tok, *spks; };
+static int flow_front(fy_flow* f, const FlowFront& w, const int32_t* token, int tok_ld, const int32_t* prompt_token, int ptok_ld, const float* embedding,
+                      int B, int Nmax, const int* d_np, const int* d_nall, const int* d_nout, hipStream_t st) {
+    const fy_flow_config& c = f->cfg;
+    const int C = c.mel;
+    hipLaunchKernelGGL(spk_k, dim3(B), dim3(256), 0, st, embedding, f->spk_w, f->spk_b, w.spks, c.spk_in, C);
+    hipLaunchKernelGGL(tok_embed_k, dim3(Nmax, B), dim3(128), 0, st, prompt_token, ptok_ld, token, tok_ld, d_np, d_nall, w.tok_all,
+                       f->emb_w, w.emb, Nmax, C, c.vocab);
+    ConvDesc d;
+    memset(&d, 0, sizeof(d));
+    d.B = B; d.dil = 1; d.stride = 1; d.up = 1; d.groups = 1; d.out_scale = 1.f;
+    d.x = w.emb; d.x_bs = (long)Nmax * C; d.x_ld = C; d.L_in = Nmax; d.in_len = d_nall;
+    d.y = w.pre_a; d.y_bs = (long)Nmax * c.pre_ch; d.y_ld = c.pre_ch; d.L_out = Nmax; d.out_len = d_nout;
+    d.Cin = C; d.Cout = c.pre_ch; d.KW = c.pre_lookahead + 1; d.pad_left = 0; d.bias = f->pre1.bias;
+    d.post_act = ACT_LEAKY; d.post_slope = 0.01f;
+    FY_TRY(conv1d_f32_mfma(d, f->pre1, st));
+    ConvDesc e;
+    memset(&e, 0, sizeof(e));
+    e.B = B; e.dil = 1; e.stride = 1; e.up = 1; e.groups = 1; e.out_scale = 1.f;
+    e.x = w.pre_a; e.x_bs = (long)Nmax * c.pre_ch; e.x_ld = c.pre_ch; e.L_in = Nmax; e.in_len = d_nout;
+    e.y = w.mu_tok; e.y_bs = (long)Nmax * C; e.y_ld = C; e.L_out = Nmax; e.out_len = d_nout;
+    e.Cin = c.pre_ch; e.Cout = C; e.KW = 3; e.pad_left = 2; e.bias = f->pre2.bias;
+    e.add_resid = 1; e.resid = w.emb; e.r_bs = (long)Nmax * C; e.r_ld = C;
+    return conv1d_f32_mfma(e, f->pre2, st);
+}
+
 extern "C" int fy_flow_infer(fy_flow* f, const int32_t* token, int32_t tok_ld, const int32_t* n_token, const int32_t* prompt_token,
                              int32_t ptok_ld, const int32_t* n_prompt, const float* prompt_feat, int32_t pfeat_rows, const int32_t* n_pfeat,
                              const float* embedding, const float* rand_noise, int32_t noise_ld, int32_t B, float* mel, int32_t mel_frames,
@@ -773,28 +905,7 @@ extern "C" int fy_flow_infer(fy_flow* f, const int32_t* token, int32_t tok_ld, c
     FY_TRY(upload_ints(f->blen, lens.data(), (int)lens.size(), st));
     FY_TRY(upload_ints(f->seq_len, sl.data(), (int)sl.size(), st));
     const int *d_nall = f->blen, *d_T = f->blen + mb, *d_pmel = f->blen + 2 * mb, *d_np = f->blen + 3 * mb, *d_nout = f->blen + 4 * mb;
-    // front: speaker projection, token embedding, PreLookahead (upsample_encoder.py:82-103)
-    hipLaunchKernelGGL(spk_k, dim3(B), dim3(256), 0, st, embedding, f->spk_w, f->spk_b, f->spks, c.spk_in, C);
-    hipLaunchKernelGGL(tok_embed_k, dim3(Nmax, B), dim3(128), 0, st, prompt_token, ptok_ld, token, tok_ld, d_np, d_nall, f->tok_all,
-                       f->emb_w, f->emb, Nmax, C, c.vocab);
-    {
-        ConvDesc d;
-        memset(&d, 0, sizeof(d));
-        d.B = B; d.dil = 1; d.stride = 1; d.up = 1; d.groups = 1; d.out_scale = 1.f;
-        d.x = f->emb; d.x_bs = (long)Nmax * C; d.x_ld = C; d.L_in = Nmax; d.in_len = d_nall;
-        d.y = f->pre_a; d.y_bs = (long)Nmax * c.pre_ch; d.y_ld = c.pre_ch; d.L_out = Nmax; d.out_len = d_nout;
-        d.Cin = C; d.Cout = c.pre_ch; d.KW = c.pre_lookahead + 1; d.pad_left = 0; d.bias = f->pre1.bias;
-        d.post_act = ACT_LEAKY; d.post_slope = 0.01f;
-        FY_TRY(conv1d_f32_mfma(d, f->pre1, st));
-        ConvDesc e;
-        memset(&e, 0, sizeof(e));
-        e.B = B; e.dil = 1; e.stride = 1; e.up = 1; e.groups = 1; e.out_scale = 1.f;
-        e.x = f->pre_a; e.x_bs = (long)Nmax * c.pre_ch; e.x_ld = c.pre_ch; e.L_in = Nmax; e.in_len = d_nout;
-        e.y = f->mu_tok; e.y_bs = (long)Nmax * C; e.y_ld = C; e.L_out = Nmax; e.out_len = d_nout;
-        e.Cin = c.pre_ch; e.Cout = C; e.KW = 3; e.pad_left = 2; e.bias = f->pre2.bias;
-        e.add_resid = 1; e.resid = f->emb; e.r_bs = (long)Nmax * C; e.r_ld = C;
-        FY_TRY(conv1d_f32_mfma(e, f->pre2, st));
-    }
+    FY_TRY(flow_front(f, FlowFront{f->tok_all, f->emb, f->pre_a, f->mu_tok, f->spks}, token, tok_ld, prompt_token, ptok_ld, embedding, B, Nmax, d_np, d_nall, d_nout, st));
     hipLaunchKernelGGL(flow_setup_k, dim3(Tmax, B), dim3(128), 0, st, f->mu_tok, prompt_feat, (long)pfeat_rows * C, rand_noise, noise_ld, d_T,
                        d_pmel, f->mu, f->cond, f->x, Tmax, Nmax, C);
     if (flags & FY_PRECISE) FY_TRY(ensure_precise(f));
@@ -836,6 +947,194 @@ extern "C" int fy_flow_infer(fy_flow* f, const int32_t* token, int32_t tok_ld, c
     for (int b = 0; b < B; ++b) {
         int F = 2 * (n_token[b] + n_prompt[b] - look) - n_pfeat[b];       // mel_len2 = h.shape[1] - prompt_feat.shape[1], flow.py:384
         FY_TRY(transpose_blc_to_bcl(f->x + ((long)b * Tmax + n_pfeat[b]) * C, mel + (long)b * C * mel_frames, 1, C, F, 0, C, 0, mel_frames, st));
+    }
+    HIP_TRY(hipGetLastError());
+    return FY_OK;
+}
+
+// ---- stream slots ---------------------------------------------------------------------------------------------------------------
+extern "C" int fy_flow_streams_close(fy_flow* f) {
+    FY_CHECK(f, FY_ERR_ARG, "fy_flow_streams_close: null handle");
+    delete f->ss;
+    f->ss = nullptr;
+    return FY_OK;
+}
+
+extern "C" int fy_flow_streams_open(fy_flow* f, int32_t n_slots, int32_t cap_frames) {
+    FY_CHECK(f && n_slots >= 1 && n_slots <= 64 && cap_frames >= 2, FY_ERR_ARG, "fy_flow_streams_open: bad arguments (slots %d in [1, 64], frames %d)", n_slots, cap_frames);
+    const fy_flow_config& c = f->cfg;
+    FY_CHECK(c.static_chunk > 0, FY_ERR_ARG, "fy_flow_streams_open: the model has no chunk mask (static_chunk %d)", c.static_chunk);
+    const size_t ns = n_slots, cap = ((size_t)cap_frames + 1) & ~(size_t)1, ncap = cap / 2 + c.pre_lookahead;
+    const size_t D = c.dim, C = c.mel, inner = (size_t)c.heads * c.head_dim, FF = D * c.ff_mult, R = 2 * ns * cap;
+    const size_t n_qkv = (size_t)c.n_timesteps * c.depth * R * 3 * inner, n_xs = (size_t)(c.n_timesteps + 1) * ns * cap * C;
+    const size_t cache_b = n_qkv * 2 + n_xs * 4;
+    const size_t work_b = R * (D * 4 * 2 + 3 * inner * 4 + C * 4 + 4 * C * 2 + D * 2 + inner * 2 + FF * 2 + 16) +
+                          ns * (ncap * (C * 4 * 2 + c.pre_ch * 4 + 4) + cap * C * 4 * 2 + C * 4) + 19 * ns * 4;
+    const size_t need = cache_b + work_b;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    // (nothing is allocated in part, and nothing silently smaller: the caller picks another cap or fewer slots)
+    FY_CHECK(need + ((size_t)1 << 30) <= free_b, FY_ERR_HIP, "fy_flow_streams_open: %d slots of %zu frames need %zu bytes (%zu per slot for the caches), %zu are free",
+             n_slots, cap, need, cache_b / ns, free_b);
+    FY_CHECK(R * 4 < ((size_t)1 << 31), FY_ERR_ARG, "fy_flow_streams_open: %zu rows are more than the row tables index", R);
+    delete f->ss;                                       // past the checks: the new session replaces the previous one
+    f->ss = nullptr;
+    FlowStreams* s = new FlowStreams();
+    s->n_slots = n_slots; s->cap = (int)cap; s->ncap = (int)ncap; s->bytes = need;
+    s->slot.resize(ns);
+    auto get = [&](auto** p, size_t n) -> int {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, n * sizeof(**p) + 256);
+        if (e != hipSuccess) { fy_set_error("fy_flow_streams_open: hipMalloc(%zu B) of %zu failed: %s", n * sizeof(**p), need, hipGetErrorString(e)); return FY_ERR_HIP; }
+        s->ptrs.push_back(q);
+        *p = static_cast<std::remove_reference_t<decltype(*p)>>(q);
+        return FY_OK;
+    };
+#define TRYS(e) do { int _r = (e); if (_r) { delete s; return _r; } } while (0)
+    TRYS(get(&s->qkv, n_qkv)); TRYS(get(&s->xs, n_xs));
+    TRYS(get(&s->tab, 19 * ns)); TRYS(get(&s->rows, R)); TRYS(get(&s->tok_all, ns * ncap));
+    TRYS(get(&s->emb, ns * ncap * C)); TRYS(get(&s->pre_a, ns * ncap * c.pre_ch)); TRYS(get(&s->mu_tok, ns * ncap * C)); TRYS(get(&s->spks, ns * C));
+    TRYS(get(&s->mu, ns * cap * C)); TRYS(get(&s->cond, ns * cap * C));
+    TRYS(get(&s->h, R * D)); TRYS(get(&s->c1, R * D)); TRYS(get(&s->qf, R * 3 * inner)); TRYS(get(&s->v, R * C));
+    TRYS(get(&s->a_in, R * 4 * C)); TRYS(get(&s->xn, R * D)); TRYS(get(&s->ao, R * inner)); TRYS(get(&s->ff, R * FF));
+#undef TRYS
+    f->ss = s;
+    return FY_OK;
+}
+
+extern "C" int64_t fy_flow_streams_bytes(const fy_flow* f) { return f && f->ss ? (int64_t)f->ss->bytes : 0; }
+
+extern "C" int fy_flow_stream_slot_reset(fy_flow* f, int32_t slot) {
+    FY_CHECK(f, FY_ERR_ARG, "fy_flow_stream_slot_reset: null handle");
+    FY_CHECK(f->ss, FY_ERR_STATE, "fy_flow_stream_slot_reset: no stream-slot session (fy_flow_streams_open)");
+    FY_CHECK(slot >= 0 && slot < f->ss->n_slots, FY_ERR_ARG, "fy_flow_stream_slot_reset: slot %d outside [0, %d)", slot, f->ss->n_slots);
+    f->ss->slot[slot] = FlowStreams::Slot();
+    return FY_OK;
+}
+
+extern "C" int fy_flow_stream_slot_rows(const fy_flow* f, int32_t slot) {
+    if (!f || !f->ss || slot < 0 || slot >= f->ss->n_slots) return -1;
+    return f->ss->slot[slot].T;
+}
+
+// One chunk pass for n listed streams.  The front runs over all T frames of each (dit_forward's layout and launches, ragged by the
+// length arrays as any batch is); the blocks then see ONLY the new rows of all streams, compact - dit_forward_inc's launch chain,
+// paid once for the call: per block one LayerNorm-modulate, one product each for qkv, out-projection, ff1 and ff2 over
+// sum_i 2 (T_i - T0_i) rows, one attention launch over the 2 n sequences (per-sequence table), and one launch that rotates and
+// stores the q | k | v rows into their slots.  Nothing inside the (step, block) loops is issued per stream.
+extern "C" int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n, const int32_t* token, int32_t tok_ld, const int32_t* n_token,
+                                     const int32_t* prompt_token, int32_t ptok_ld, const int32_t* n_prompt, const float* prompt_feat, int32_t pfeat_rows,
+                                     const int32_t* n_pfeat, const float* embedding, const float* rand_noise, int32_t noise_ld, float* mel,
+                                     int32_t mel_frames, uint32_t flags, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(f && slots && token && n_token && n_prompt && n_pfeat && embedding && rand_noise && mel, FY_ERR_ARG, "fy_flow_infer_streams: null argument");
+    FY_CHECK(f->ss, FY_ERR_STATE, "fy_flow_infer_streams: no stream-slot session (fy_flow_streams_open)");
+    FlowStreams& S = *f->ss;
+    const fy_flow_config& c = f->cfg;
+    FY_CHECK(n >= 1 && n <= S.n_slots, FY_ERR_ARG, "fy_flow_infer_streams: %d streams outside [1, %d]", n, S.n_slots);
+    FY_CHECK((flags & FY_STREAMING) && (flags & FY_NO_FINALIZE) && !(flags & (FY_PRECISE | FY_DIRECT)), FY_ERR_ARG,
+             "fy_flow_infer_streams: needs FY_STREAMING | FY_NO_FINALIZE and the default arithmetic (flags %u)", flags);
+    const int C = c.mel, D = c.dim, inner = c.heads * c.head_dim, FF = D * c.ff_mult, ns = S.n_slots, cap = S.cap, look = c.pre_lookahead, chunk = c.static_chunk;
+    std::vector<int> tab(19 * ns, 0), T0s(n), Ts(n);
+    int* h_atab = tab.data();
+    int* h_stab = tab.data() + 8 * ns;
+    int* h_sl = tab.data() + 12 * ns;
+    int* h_len = tab.data() + 14 * ns;
+    int Tp = 0, Nmax = 0, Mn = 0;
+    for (int i = 0; i < n; ++i) {
+        FY_CHECK(slots[i] >= 0 && slots[i] < ns, FY_ERR_ARG, "fy_flow_infer_streams: slot %d outside [0, %d)", slots[i], ns);
+        for (int j = 0; j < i; ++j) FY_CHECK(slots[j] != slots[i], FY_ERR_ARG, "fy_flow_infer_streams: slot %d listed twice", slots[i]);
+        const int n_all = n_token[i] + n_prompt[i], T = 2 * (n_all - look);
+        FY_CHECK(n_token[i] >= 1 + look && n_prompt[i] >= 0 && n_pfeat[i] >= 0 && n_pfeat[i] <= T && T <= cap && T <= noise_ld &&
+                     T - n_pfeat[i] <= mel_frames && n_token[i] <= tok_ld && n_prompt[i] <= ptok_ld && n_pfeat[i] <= pfeat_rows,
+                 FY_ERR_ARG, "fy_flow_infer_streams: utterance %d has inconsistent lengths (tokens %d, prompt %d, prompt frames %d, frames per slot %d)",
+                 i, n_token[i], n_prompt[i], n_pfeat[i], cap);
+        // the single stream's rules, per slot (fy_flow_infer): extend from a chunk boundary with the same prompt and no fewer tokens,
+        // anything else computes the slot's stream in full
+        const FlowStreams::Slot& sl = S.slot[slots[i]];
+        int T0 = sl.T;
+        if (T % chunk != 0 || T0 % chunk != 0 || T0 >= T) T0 = 0;
+        if (n_prompt[i] != sl.np || n_pfeat[i] != sl.npf || n_token[i] < sl.ntok) T0 = 0;
+        T0s[i] = T0; Ts[i] = T;
+        h_len[0 * ns + i] = n_all; h_len[1 * ns + i] = T; h_len[2 * ns + i] = n_pfeat[i]; h_len[3 * ns + i] = n_prompt[i]; h_len[4 * ns + i] = n_all - look;
+        h_sl[2 * i] = h_sl[2 * i + 1] = T;
+        h_stab[4 * i] = slots[i]; h_stab[4 * i + 1] = T0; h_stab[4 * i + 2] = T; h_stab[4 * i + 3] = Mn;
+        for (int sq = 0; sq < 2; ++sq) {
+            int* a = h_atab + 4 * (2 * i + sq);
+            a[0] = T0; a[1] = T; a[2] = slots[i] * 2 * cap + sq; a[3] = Mn + sq;
+        }
+        Mn += 2 * (T - T0);
+        Tp = std::max(Tp, T); Nmax = std::max(Nmax, n_all);
+    }
+    for (int i = 0; i < n; ++i) {                       // past the checks: the call will run, the slots' records move
+        FlowStreams::Slot& sl = S.slot[slots[i]];
+        sl.np = n_prompt[i]; sl.npf = n_pfeat[i]; sl.ntok = n_token[i];
+        sl.T = Ts[i] % chunk == 0 ? Ts[i] : 0;          // a stream that ends off a chunk boundary keeps nothing a later call could extend
+    }
+    FY_TRY(upload_ints(S.tab, tab.data(), (int)tab.size(), st));
+    const DitSeqTab* d_atab = reinterpret_cast<const DitSeqTab*>(S.tab);
+    const int *d_stab = S.tab + 8 * ns, *d_sl = S.tab + 12 * ns, *d_len = S.tab + 14 * ns;
+    const int *d_nall = d_len, *d_pmel = d_len + 2 * ns, *d_np = d_len + 3 * ns, *d_nout = d_len + 4 * ns;
+    FY_TRY(flow_front(f, FlowFront{S.tok_all, S.emb, S.pre_a, S.mu_tok, S.spks}, token, tok_ld, prompt_token, ptok_ld, embedding, n, Nmax, d_np, d_nall, d_nout, st));
+    hipLaunchKernelGGL(stream_rows_k, dim3(cdiv(Mn, 256)), dim3(256), 0, st, d_stab, n, Tp, cap, S.rows, Mn);
+    const size_t xslice = (size_t)ns * cap * C, qslice = (size_t)ns * 2 * cap * 3 * inner;
+    hipLaunchKernelGGL(stream_setup_k, dim3(Tp, n), dim3(128), 0, st, S.mu_tok, prompt_feat, (long)pfeat_rows * C, rand_noise, noise_ld, d_stab, d_pmel,
+                       S.mu, S.cond, S.xs, Tp, Nmax, cap, C);
+    const int nseq = 2 * n, Mf = nseq * Tp;
+    const bool mf = f->pos1.w_mfma != nullptr;
+    for (int step = 0; step < c.n_timesteps; ++step) {
+        const float* xs = S.xs + step * xslice;
+        hipLaunchKernelGGL(stream_assemble_k, dim3(Tp, nseq), dim3(4 * C), 0, st, xs, S.cond, S.mu, S.spks, d_stab, S.a_in, Tp, cap, C);
+        GemmEpi e;
+        e.bias = f->b_in; e.out = S.h; e.out_bf16 = 0; e.ldc = D;
+        FY_TRY(gemm_bf16(S.a_in, 4 * C, f->w_in, Mf, D, 4 * C, e, st));
+        {
+            ConvDesc d;
+            memset(&d, 0, sizeof(d));
+            d.B = nseq; d.dil = 1; d.stride = 1; d.up = 1; d.groups = c.conv_pos_groups; d.out_scale = 1.f;
+            d.x = S.h; d.x_bs = (long)Tp * D; d.x_ld = D; d.L_in = Tp; d.in_len = d_sl;
+            d.y = S.c1; d.y_bs = (long)Tp * D; d.y_ld = D; d.L_out = Tp; d.out_len = d_sl;
+            d.Cin = D; d.Cout = D; d.KW = c.conv_pos_k; d.pad_left = c.conv_pos_k - 1; d.bias = f->pos1.bias; d.post_act = ACT_MISH;
+            FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos1, false, st) : conv1d_f32_direct(d, f->pos1, st));
+            d.x = S.c1; d.y = S.h; d.bias = f->pos2.bias;
+            d.add_resid = 1; d.resid = S.h; d.r_bs = (long)Tp * D; d.r_ld = D;
+            FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos2, false, st) : conv1d_f32_direct(d, f->pos2, st));
+        }
+        float* h = S.c1;                                 // the compact residual stream
+        hipLaunchKernelGGL(stream_gather_k, dim3(Mn), dim3(256), 0, st, S.h, S.rows, h, D);
+        const float* modbase = f->mod + (size_t)step * c.depth * 6 * D;
+        for (int i = 0; i < c.depth; ++i) {
+            const FlowBlockW& k = f->blk[i];
+            const float* m = modbase + (size_t)i * 6 * D;
+            bf16_t* qkv = S.qkv + ((size_t)step * c.depth + i) * qslice;
+            hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + D, m, S.xn, (bf16_t*)nullptr, Mn, D);
+            GemmEpi q;
+            q.bias = k.bqkv; q.out = S.qf; q.out_bf16 = 0; q.ldc = 3 * inner;
+            FY_TRY(gemm_bf16(S.xn, D, k.wqkv, Mn, 3 * inner, D, q, st));
+            hipLaunchKernelGGL(stream_qkv_store_k, dim3(Mn), dim3(256), 0, st, S.qf, S.rows, f->rope, qkv, 3 * inner, c.head_dim / 2, inner);
+            FY_TRY(dit_attention_tab(qkv, S.ao, d_atab, nseq, Tp, c.heads, chunk, 2, st));
+            GemmEpi o;
+            o.mode = EPI_GATE_RESID; o.bias = k.bo; o.resid = h; o.gate = m + 2 * D; o.ldc = D;
+            FY_TRY(gemm_bf16(S.ao, inner, k.wo, Mn, D, inner, o, st));
+            hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + 4 * D, m + 3 * D, S.xn, (bf16_t*)nullptr, Mn, D);
+            GemmEpi g;
+            g.bias = k.b1; g.act = ACT_GELU_TANH; g.out = S.ff; g.out_bf16 = 1; g.ldc = FF;
+            FY_TRY(gemm_bf16(S.xn, D, k.w1, Mn, FF, D, g, st));
+            GemmEpi r;
+            r.mode = EPI_GATE_RESID; r.bias = k.b2; r.resid = h; r.gate = m + 5 * D; r.ldc = D;
+            FY_TRY(gemm_bf16(S.ff, FF, k.w2, Mn, D, FF, r, st));
+        }
+        const float* fn = f->fin + (size_t)step * 2 * D;
+        hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, fn, fn + D, S.xn, (bf16_t*)nullptr, Mn, D);
+        GemmEpi p;
+        p.bias = f->b_out; p.out = S.v; p.out_bf16 = 0; p.ldc = C;
+        FY_TRY(gemm_bf16(S.xn, D, f->w_out, Mn, C, D, p, st));
+        hipLaunchKernelGGL(stream_euler_k, dim3(Mn / 2), dim3(128), 0, st, xs, S.xs + (step + 1) * xslice, S.v, S.rows, cap, C, f->dt_of_step[step], c.cfg_rate);
+    }
+    const float* xe = S.xs + c.n_timesteps * xslice;
+    for (int i = 0; i < n; ++i) {
+        const int F = Ts[i] - n_pfeat[i];
+        FY_TRY(transpose_blc_to_bcl(xe + ((size_t)slots[i] * cap + n_pfeat[i]) * C, mel + (long)i * C * mel_frames, 1, C, F, 0, C, 0, mel_frames, st));
     }
     HIP_TRY(hipGetLastError());
     return FY_OK;

@@ -55,6 +55,20 @@ struct GemmEpi {
 void gemm_set_stamps(unsigned long long* p);
 #endif
 
+// The rotation of two interleaved pairs, v = (a, b, c, d), t = (cos0, sin0, cos1, sin1): out = t * cos + rotate_half(t) * sin as the
+// reference computes it (x-transformers apply_rotary_pos_emb: two multiplies and an add, each rounded).  Floating-point contraction is
+// OFF here: left to the compiler, one instantiation of an epilogue fused a multiply-add where another did not, and tilings that
+// accumulate K in the same order came out 3-6 bf16 roundings apart in 20 M outputs - big calls and small calls of the estimator must
+// agree bit for bit (tests/test_flow_gpu.py::test_bench_sized_estimator_equals_pairs, the incremental stream's chunks).  In this header because
+// the flow decoder's stream slots rotate the fp32 sums of their qkv product in a launch of their own (flow.hip: stream_qkv_store_k).
+__device__ __forceinline__ void rope_rotate(float4& v, const float4& t) {
+#pragma clang fp contract(off)
+    const float a = v.x, b = v.y, c = v.z, d = v.w;
+    const float ac = a * t.x, bs = b * t.y, bc = b * t.x, as = a * t.y, cc = c * t.z, ds = d * t.w, dc = d * t.z, cs = c * t.w;
+    v.x = ac - bs; v.y = bc + as;
+    v.z = cc - ds; v.w = dc + cs;
+}
+
 extern int gemm_tile_override;     // microbenchmarks only: 0 = automatic choice (gemm.hip lists the forms)
 // A: bf16 [M][lda]; W: bf16 [N][K] (K % 64 == 0); M, N arbitrary
 int gemm_bf16(const bf16_t* A, int lda, const bf16_t* W, int M, int N, int K, const GemmEpi& epi, hipStream_t st);

@@ -47,18 +47,7 @@ __device__ __forceinline__ void split8_3(const float4& a, const float4& b, uint4
     lo = make_uint4(l[0] | (l[1] << 16), l[2] | (l[3] << 16), l[4] | (l[5] << 16), l[6] | (l[7] << 16));
 }
 
-// The rotation of two interleaved pairs, v = (a, b, c, d), t = (cos0, sin0, cos1, sin1): out = t * cos + rotate_half(t) * sin as the
-// reference computes it (x-transformers apply_rotary_pos_emb: two multiplies and an add, each rounded).  Floating-point contraction is
-// OFF here: left to the compiler, one instantiation of an epilogue fused a multiply-add where another did not, and tilings that
-// accumulate K in the same order came out 3-6 bf16 roundings apart in 20 M outputs - big calls and small calls of the estimator must
-// agree bit for bit (tests/test_flow_gpu.py::test_bench_sized_estimator_equals_pairs, the incremental stream's chunks).
-__device__ __forceinline__ void rope_rotate(float4& v, const float4& t) {
-#pragma clang fp contract(off)
-    const float a = v.x, b = v.y, c = v.z, d = v.w;
-    const float ac = a * t.x, bs = b * t.y, bc = b * t.x, as = a * t.y, cc = c * t.z, ds = d * t.w, dc = d * t.z, cs = c * t.w;
-    v.x = ac - bs; v.y = bc + as;
-    v.z = cc - ds; v.w = dc + cs;
-}
+// (rope_rotate, the rotation of two interleaved pairs every rotary epilogue shares: gemm.h)
 
 // Sum over the 16 lanes of a DPP row (lanes 16 k .. 16 k + 15), the same value and the same order of additions in every lane: pairs,
 // quads (quad permutes), the two quads of a half (half-row mirror), the two halves (row mirror) - vector-ALU data movement, no trip

@@ -19,6 +19,49 @@ def reference_t_span(n_timesteps: int) -> torch.Tensor:
     return 1 - torch.cos(t * 0.5 * torch.pi)
 
 
+def stream_chunk_plan(n_tokens: int, n_prompt_tokens: int, hop: int = 25, look: int = 3):
+    """The reference's stream=True chunk schedule (cli/model.py:339-369) as a pure function of the token count: a chunk is cut
+    whenever hop + look tokens beyond the offset exist, the first hop padded so that prompt + hop is a multiple of `hop`; the
+    rest is the final pass.  -> [(n_in, offset, finalize)]: the call sees tokens [:n_in] and yields the mel of tokens
+    [offset : n_in - look] (finalize: [offset : n_in])."""
+    pad = -(-n_prompt_tokens // hop) * hop - n_prompt_tokens
+    plan, offset = [], 0
+    while True:
+        need = offset + (hop + pad if offset == 0 else hop) + look
+        if need > n_tokens:
+            break
+        plan.append((need, offset, False))
+        offset = need - look
+    plan.append((n_tokens, offset, True))
+    return plan
+
+
+def stream_poll_plan(n_tokens: Sequence[int], n_prompt_tokens: Sequence[int], tokens_per_poll: int = 25, hop: int = 25, look: int = 3):
+    """The schedule of K streams that share one lane (CosyVoice3Model.tts_stream_batch): every poll the LM adds up to
+    `tokens_per_poll` tokens to each unfinished stream, then ONE batched flow call takes every stream whose next chunk is complete
+    (at most one chunk per stream and poll) and one batched final pass the streams whose tokens have ended.
+    -> [poll] of [(stream, n_in, offset, finalize)]; a stream's own entries are `stream_chunk_plan`'s, whoever else is live."""
+    K = len(n_tokens)
+    have, offset, ended = [0] * K, [0] * K, [False] * K
+    pads = [-(-p // hop) * hop - p for p in n_prompt_tokens]
+    polls = []
+    while not all(ended):
+        poll = []
+        for i in range(K):
+            if ended[i]:
+                continue
+            have[i] = min(n_tokens[i], have[i] + tokens_per_poll)
+            need = offset[i] + (hop + pads[i] if offset[i] == 0 else hop) + look
+            if have[i] >= need:
+                poll.append((i, need, offset[i], False))
+                offset[i] = need - look
+            elif have[i] == n_tokens[i]:
+                poll.append((i, n_tokens[i], offset[i], True))
+                ended[i] = True
+        polls.append(poll)
+    return polls
+
+
 def _cfg_struct(cfg: FlowCfg) -> _lib.FlowConfig:
     c = _lib.FlowConfig()
     _lib.lib().fy_flow_default_config(C.byref(c))
@@ -110,6 +153,57 @@ class FlowEngine:
     def stream_rows(self) -> int:
         """Mel rows the incremental calls of the current stream have kept (0: the next call computes everything)."""
         return int(_lib.lib().fy_flow_stream_rows(self._h))
+
+    # ---- stream slots: several stream=True utterances share one chunk pass (include/fy_cosy3.h) ----
+    def open_streams(self, n_slots: int, cap_frames: int):
+        """A session of n_slots incremental caches of cap_frames mel rows (prompt + generated) each; raises FyError when the
+        device does not have the memory (2.7 MB per frame row and slot at full size)."""
+        with torch.cuda.device(self.device):
+            check(_lib.lib().fy_flow_streams_open(self._h, n_slots, cap_frames))
+
+    def close_streams(self):
+        check(_lib.lib().fy_flow_streams_close(self._h))
+
+    @property
+    def streams_bytes(self) -> int:
+        """Device bytes of the open stream-slot session (0: none)."""
+        return int(_lib.lib().fy_flow_streams_bytes(self._h))
+
+    def stream_slot_reset(self, slot: int):
+        """The slot's next `inference_streams` call starts a new stream."""
+        check(_lib.lib().fy_flow_stream_slot_reset(self._h, slot))
+
+    def stream_slot_rows(self, slot: int) -> int:
+        """Mel rows the slot's stream has kept (0: its next call computes everything)."""
+        return int(_lib.lib().fy_flow_stream_slot_rows(self._h, slot))
+
+    def inference_streams(self, slots: Sequence[int], token: torch.Tensor, n_token: Sequence[int], prompt_token: torch.Tensor,
+                          n_prompt: Sequence[int], prompt_feat: torch.Tensor, n_pfeat: Sequence[int], embedding: torch.Tensor,
+                          rand_noise: torch.Tensor, flags: int = 0) -> torch.Tensor:
+        """One chunk pass for the streams in `slots`: row i of the inputs (shaped as `inference`'s) extends the stream of
+        slots[i].  Always streaming=True, finalize=False.  -> mel (n, 80, 2*max(n_token)); row i is valid in
+        [:, :2*(n_token[i] - pre_lookahead)] and equals `inference(..., streaming=True, finalize=False)` on utterance i alone."""
+        flags |= FY_STREAMING | FY_NO_FINALIZE
+        n = len(slots)
+        dev = self.device
+        token = token.to(dev, torch.int32).contiguous()
+        prompt_token = prompt_token.to(dev, torch.int32).contiguous()
+        if prompt_token.shape[1] == 0:
+            prompt_token = torch.zeros(n, 1, dtype=torch.int32, device=dev)
+        prompt_feat = prompt_feat.to(dev, torch.float32).contiguous()
+        if prompt_feat.shape[1] == 0:
+            prompt_feat = torch.zeros(n, 1, self.cfg.mel, device=dev)
+        embedding = embedding.to(dev, torch.float32).contiguous()
+        noise = rand_noise.reshape(self.cfg.mel, -1).to(dev, torch.float32).contiguous()
+        assert token.shape[0] == n and prompt_token.shape[0] == n and prompt_feat.shape[0] == n and embedding.shape[0] == n
+        frames = 2 * max(int(v) for v in n_token)
+        mel = torch.zeros(n, self.cfg.mel, frames, device=dev, dtype=torch.float32)
+        check(_lib.lib().fy_flow_infer_streams(self._h, _lib.int_array(slots), n, token.data_ptr(), token.shape[1], _lib.int_array(n_token),
+                                               prompt_token.data_ptr(), prompt_token.shape[1], _lib.int_array(n_prompt),
+                                               prompt_feat.data_ptr(), prompt_feat.shape[1], _lib.int_array(n_pfeat),
+                                               embedding.data_ptr(), noise.data_ptr(), noise.shape[1], mel.data_ptr(), frames,
+                                               flags, self._stream()))
+        return mel
 
     def speed(self, mel: torch.Tensor, speed: float) -> torch.Tensor:
         """cli/model.py:435-437: F.interpolate(mel, size=int(F / speed), mode="linear") on (B, 80, F)."""

@@ -173,6 +173,35 @@ int fy_flow_stream_reset(fy_flow* f);
 /* mel rows (prompt + generated frames) the incremental calls of the current stream have kept; 0 = nothing (the next call computes all) */
 int fy_flow_stream_rows(const fy_flow* f);
 
+/* Stream slots: several stream=True utterances share one chunk pass.  A session gives the handle n_slots incremental caches (what
+ * FY_INCREMENTAL keeps for its one stream: the q | k | v rows of every (Euler step, block) and the ODE state of every step) at a
+ * pitch of cap_frames mel rows (prompt + generated) each, and the work buffers of the batched call; the single-stream state above
+ * is separate and untouched.  Calls of a session are serial on one stream.
+ * fy_flow_streams_open: allocates everything or nothing - at full size 2.7 MB per frame row and slot plus ~34 KB per row of work
+ * buffers; FY_ERR_HIP with the bytes asked for when the device does not have them (no smaller fallback).  Opening again replaces
+ * the session.  fy_flow_streams_close frees it; fy_flow_streams_bytes: the session's device bytes (0: none).
+ * fy_flow_stream_slot_reset: the slot's next call starts a new stream.  fy_flow_stream_slot_rows: mel rows the slot has kept
+ * (0: the next call computes everything; -1: no such slot).                                                                        */
+int fy_flow_streams_open(fy_flow* f, int32_t n_slots, int32_t cap_frames);
+int fy_flow_streams_close(fy_flow* f);
+int64_t fy_flow_streams_bytes(const fy_flow* f);
+int fy_flow_stream_slot_reset(fy_flow* f, int32_t slot);
+int fy_flow_stream_slot_rows(const fy_flow* f, int32_t slot);
+/* Advance the streams in slots[0 .. n) (host int32, distinct) by one chunk each in ONE pass: utterance i of the inputs (packed
+ * over the n utterances as fy_flow_infer's over B) extends the stream of slots[i]; mel out (n, 80, mel_frames), utterance i fills
+ * frames [0, 2 * (n_token[i] - pre_lookahead)).  flags: FY_STREAMING | FY_NO_FINALIZE, default arithmetic.  Every slot follows
+ * FY_INCREMENTAL's rules on its own: it extends when its previous call and this one end on a chunk boundary with the same prompt
+ * lengths and no fewer tokens, otherwise its stream is computed in full (and kept, unless this call ends off a boundary).  Streams
+ * may be at different chunk indices and lengths; a slot's first call brings all of its rows.  The new rows of all listed streams go
+ * through every DiT product together, so the launch chain of a chunk pass is paid once per call; the results are bit for bit those
+ * of fy_flow_infer(FY_STREAMING | FY_NO_FINALIZE) on each utterance alone.  FY_ERR_ARG (before any device work, the session as it
+ * was): a slot out of range or listed twice, 2 * (tokens + prompt - look-ahead) above cap_frames, other flags; FY_ERR_STATE: no
+ * session.  Lengths travel as kernel arguments: the call does not wait on the host.                                               */
+int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n, const int32_t* token, int32_t tok_ld, const int32_t* n_token,
+                          const int32_t* prompt_token, int32_t ptok_ld, const int32_t* n_prompt, const float* prompt_feat,
+                          int32_t pfeat_rows, const int32_t* n_pfeat, const float* embedding, const float* rand_noise, int32_t noise_ld,
+                          float* mel, int32_t mel_frames, uint32_t flags, void* stream);
+
 /* replaces the estimator hand-off ConditionalCFM.forward_estimator uses for a non-nn.Module estimator
  *   cosyvoice/flow/flow_matching.py:126-153: contiguous x (B2,80,T), mask (B2,1,T), mu (B2,80,T), t (B2),
  *   spks (B2,80), cond (B2,80,T); the result overwrites x.                                                   */
