@@ -91,6 +91,14 @@ def _declare(L):
     L.fy_hift_stream_reset.argtypes = [vp]
     L.fy_hift_stream_samples.argtypes = [vp]
     L.fy_hift_stream_window.argtypes = [vp]
+    L.fy_hift_streams_open.argtypes = [vp, i32]
+    L.fy_hift_streams_close.argtypes = [vp]
+    L.fy_hift_streams_bytes.argtypes = [vp]
+    L.fy_hift_streams_bytes.restype = C.c_int64
+    L.fy_hift_stream_slot_reset.argtypes = [vp, i32]
+    L.fy_hift_stream_slot_samples.argtypes = [vp, i32]
+    L.fy_hift_stream_slot_window.argtypes = [vp, i32]
+    L.fy_hift_infer_streams.argtypes = [vp, i32p, i32, C.POINTER(vp), i32p, i32p, i32p, f32p, f32p, f32p, i32, i32p, u32, vp]
     L.fy_flow_default_config.argtypes = [C.POINTER(FlowConfig)]
     L.fy_flow_default_config.restype = None
     L.fy_flow_create.argtypes = [C.POINTER(vp), C.POINTER(FlowConfig), C.POINTER(FyTensor), i32, i32, i32, vp]

@@ -123,7 +123,6 @@ class CosyVoice3Model:
         fb = max_batch * self.flow_group
         self.flow = FlowEngine(flow_weights, cfg.flow, max_batch=fb, max_frames=max_frames, device=self.device)
         self.hift = HiftEngine(hift_weights, cfg.hift, max_batch=fb, max_frames=2 * max_tokens, device=self.device)
-        self._hift_weights = hift_weights     # tts_stream_batch builds one small vocoder handle per stream slot on first use
         # The reference lets several threads enter tts() on one model object (a gRPC pool, runtime/python/grpc/server.py:68-69;
         # per-call state keyed by uuid, cli/model.py:330-333).  An engine handle is single-threaded, so concurrent calls each
         # take a LANE - an own (LM, flow, vocoder) handle set and stream; `concurrency` lanes exist (the reference's
@@ -750,10 +749,11 @@ class CosyVoice3Model:
     @torch.inference_mode()
     def tts_stream_batch(self, inputs: Sequence[Dict[str, torch.Tensor]]):
         """K stream=True generations through one lane: one LM slot session (`open_slots / join / step / release`, stepped
-        `token_hop_len` tokens per poll) and one flow stream-slot session.  Every poll runs ONE `FlowEngine.inference_streams` call
-        for all streams whose next hop + look-ahead tokens exist, then each such stream's incremental vocoder (a HiftEngine per
-        stream slot), and yields (index, {'tts_speech': (1, S) on CPU}).  A stream whose LM has ended gets the reference's final pass
-        (finalize=True, no chunk mask; the plain `inference`, batched over the streams that end in the same poll).  Each stream's
+        `token_hop_len` tokens per poll), one flow stream-slot session and one vocoder stream-slot session on the lane's own engines.
+        Every poll runs ONE `FlowEngine.inference_streams` call for all streams whose next hop + look-ahead tokens exist; a stream
+        whose LM has ended gets the reference's final flow pass (finalize=True, no chunk mask; the plain `inference`, batched over
+        the streams that end in the same poll); then ONE `HiftEngine.inference_streams` call vocodes the new samples of all of them
+        (chunks and final passes together), and the poll yields (index, {'tts_speech': (1, S) on CPU}) per stream.  Each stream's
         chunks are those `tts(stream=True)` yields for it alone: the chunk boundaries depend on its token count only
         (`flow.stream_chunk_plan`) and the LM's ids on its own inputs.  Under the "ras" sampler stream i draws from row i of the
         call's uniforms."""
@@ -765,35 +765,29 @@ class CosyVoice3Model:
         pspeech = [d.get("llm_prompt_speech_token", z).reshape(-1).tolist() for d in inputs]
         self._check_capacity(inputs, None)
         ptok, n_fp, pfeat, n_pf, emb = self._prompt_tensors(inputs)
-        look, hop, up = self.cfg.flow.pre_lookahead, self.token_hop_len, self.cfg.hift.upsample_total
+        look, hop = self.cfg.flow.pre_lookahead, self.token_hop_len
         pads = [-(-p // hop) * hop - p for p in n_fp]
         ln = self._acquire_lane()
         opened = False
         try:
-            hifts = ln.__dict__.setdefault("stream_hifts", [ln.hift])
-            while len(hifts) < K:
-                hifts.append(HiftEngine(self._hift_weights, self.cfg.hift, max_batch=1, max_frames=2 * self.max_tokens, device=self.device))
             with self._lane_stream(ln):
                 self._arm_lane_sampler(ln, self._next_batch_ids(), K)
                 out, _, _ = ln.llm.open_slots(self.max_tokens)
                 ln.llm.join(list(range(K)), text, ptext, pspeech)
                 ln.flow.open_streams(K, 2 * (self.max_tokens + self.max_prompt_tokens))
                 opened = True
+                # K <= self.max_batch (asserted above) <= ln.hift.max_batch (every lane's vocoder is built with at least max_batch
+                # rows), so K slots always fit; and a poll's n <= K windows of at most 2 * max_tokens frames fit its buffers
+                ln.hift.open_streams(K)
                 for i in range(K):
                     ln.flow.stream_slot_reset(i)
-                    hifts[i].stream_reset()
-            offset, speech, mel_all, live = [0] * K, [0] * K, [None] * K, set(range(K))
+                    ln.hift.stream_slot_reset(i)
+            offset, mel_all, live = [0] * K, [None] * K, set(range(K))
 
-            def vocode(i, mel, n_in, finalize):
+            def grow(i, mel, n_in, finalize):
                 valid = 2 * (n_in if finalize else n_in - look)
                 mel = mel[:, :, 2 * offset[i]: valid]
                 mel_all[i] = mel if mel_all[i] is None else torch.cat([mel_all[i], mel], dim=2)
-                wav, _ = hifts[i].inference(mel_all[i].contiguous(), self.rand_ini, self.sine_noise, finalize=finalize, flags=self.hift_flags,
-                                            incremental=True)
-                end = up * (mel_all[i].shape[2] if finalize else mel_all[i].shape[2] - 8)
-                res = wav[:, speech[i]:end].cpu()
-                speech[i] = end
-                return res
 
             while live:
                 results = []
@@ -808,7 +802,7 @@ class CosyVoice3Model:
                                                         [n_fp[i] for i in ready], pfeat[ix], [n_pf[i] for i in ready], emb[ix], self.rand_noise,
                                                         flags=self.flow_flags)
                         for j, i in enumerate(ready):
-                            results.append((i, vocode(i, mel[j: j + 1], need[i], False)))
+                            grow(i, mel[j: j + 1], need[i], False)
                             offset[i] = need[i] - look
                     for g in range(0, len(ended), ln.flow.max_batch):
                         grp = ended[g: g + ln.flow.max_batch]
@@ -818,15 +812,23 @@ class CosyVoice3Model:
                         mel = ln.flow.inference(out[ix, : max(n[i] for i in grp)].contiguous(), [n[i] for i in grp], ptok[ix], [n_fp[i] for i in grp],
                                                 pfeat[ix], [n_pf[i] for i in grp], emb[ix], self.rand_noise, flags=self.flow_flags)
                         for j, i in enumerate(grp):
-                            results.append((i, vocode(i, mel[j: j + 1], n[i], True)))
+                            grow(i, mel[j: j + 1], n[i], True)
                             ln.llm.release(i)
                             ln.flow.stream_slot_reset(i)
                             live.discard(i)
+                    if ready or ended:
+                        # one vocoder pass for the poll (csrc/hift.hip: fy_hift_infer_streams): slot i continues stream i over its new
+                        # frames plus a fixed margin - the same samples as a run over its whole mel so far
+                        todo = ready + ended
+                        wavs = ln.hift.inference_streams(todo, [mel_all[i] for i in todo], self.rand_ini, self.sine_noise,
+                                                         [i in ended for i in todo], flags=self.hift_flags)
+                        results = [(i, w[None].cpu()) for i, w in zip(todo, wavs)]
                 for i, wav in results:
                     yield i, {"tts_speech": wav}
         finally:
             if opened:
                 ln.flow.close_streams()
+                ln.hift.close_streams()
             self._release_lane(ln)
 
     # ------------------------------------------------------------------ reference-shaped path

@@ -47,6 +47,14 @@ struct fy_hift {
     long inc_samples = 0;
     int inc_frames = 0, inc_window = 0;
     double* inc_phase = nullptr;
+    // stream slots (fy_hift_streams_open): per slot what inc_* hold for the single stream - the phase sums at a pitch of ss_pitch
+    // doubles per slot (device) - and the per-row table of a batched call (device, SROW ints per row; hift_infer_streams)
+    struct Slot { long samples = 0; int frames = 0, window = 0; bool big = false; };      // big: the f0 convs' form of the last call
+    std::vector<Slot> ss;
+    double* ss_phase = nullptr;
+    int* ss_tab = nullptr;
+    int ss_pitch = 0;
+    size_t ss_bytes = 0;
     int L(int stage, int F) const {                  // rows of stage tensors for F frames
         int l = F;
         for (int i = 0; i <= stage; ++i) l *= cfg.ups[i];
@@ -76,6 +84,8 @@ static void source_down_shape(const fy_hift_config& c, int i, int* k, int* strid
 }
 
 fy_hift::~fy_hift() {
+    if (ss_phase) (void)hipFree(ss_phase);
+    if (ss_tab) (void)hipFree(ss_tab);
     conv_free(w.conv_pre); conv_free(w.conv_post);
     for (int i = 0; i < N_UP; ++i) { conv_free(w.ups[i]); conv_free(w.source_downs[i]); conv_free(sd_mfma[i]); conv_free(ups_poly[i]); }
     for (int i = 0; i < 5; ++i) conv_free(w.f0c[i]);
@@ -423,18 +433,129 @@ static int init_tables() {
     return FY_OK;
 }
 
+// ---- stream slots: one FY_INCREMENTAL pass over several streams -------------------------------------------------------------------
+// Batch row b of a call is one stream; what the single stream's kernels take as one value per call (mel_window_k, sine_phase_k,
+// source_k, istft16_k) these take per row from a table in device memory (SROW ints per row, written by upload_ints: no copy engine,
+// no stream synchronisation).  Everything between is the ragged batch path (hift_f0, stft16_k, hift_decode) over h->lens.
+#define SROW 12
+enum { SR_SLOT = 0, SR_W, SR_LD, SR_A0, SR_ANEXT, SR_NLO, SR_WAVROW, SR_MEL_LO, SR_MEL_HI };
+
+// mel_window_k per row: stream b's mel (C, ld_b) at the table's pointer, frames [W_b, W_b + frames[b]) -> channels-last rows of batch row b
+__global__ void mel_windows_k(const int* __restrict__ tab, float* __restrict__ dst, const int* __restrict__ frames, int C, int Fmax) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z, L = frames[b];
+    const int c0 = blockIdx.y * 32, l0 = blockIdx.x * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    if (l0 >= L) return;
+    const int* t = tab + b * SROW;
+    const float* src = reinterpret_cast<const float*>(((unsigned long long)(unsigned)t[SR_MEL_HI] << 32) | (unsigned)t[SR_MEL_LO]);
+    const int ld = t[SR_LD], f_lo = t[SR_W];
+    float* out = dst + (long)b * Fmax * C;
+    for (int i = ty; i < 32; i += 8) {
+        const int c = c0 + i, l = l0 + tx;
+        tile[i][tx] = (c < C && l < L) ? src[(long)c * ld + f_lo + l] : 0.f;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+        const int l = l0 + i, c = c0 + tx;
+        if (c < C && l < L) out[(long)l * C + c] = tile[tx][i];
+    }
+}
+
+// sine_phase_k with the carry per slot: row b continues from its slot's sums at its own a0 and leaves the sums at its own a_next
+// there.  Per harmonic the same sequence of double additions as sine_phase_k performs for that stream alone.
+__global__ void sine_phase_slots_k(const float* __restrict__ f0, float* __restrict__ sines, const int* __restrict__ frames, const int* __restrict__ tab,
+                                   int Fmax, int H1, float sr, float amp, float up, double* __restrict__ phase, int pitch) {
+    int b = blockIdx.x, hm = threadIdx.x;
+    if (hm >= H1) return;
+    const int* tb = tab + b * SROW;
+    double* carry = phase + (long)tb[SR_SLOT] * pitch;
+    const int a0 = tb[SR_A0], a_next = tb[SR_ANEXT];
+    int n = frames[b];
+    double cum = 0.0;
+    const float mult = (float)(hm + 1);
+    for (int t = 0; t < n; ++t) {
+        if (t == a0) cum = carry[hm];
+        if (t == a_next) carry[hm] = cum;
+        float fn = f0[(long)b * Fmax + t] * mult;
+        float q = fn / sr;
+        float rad = q - floorf(q);
+        float ds = 0.5f * rad + 0.5f * rad;
+        cum += (double)ds;
+        float ph = (float)cum;
+        ph = ph * 2.0f;
+        ph = ph * 3.14159265358979323846f;
+        ph = ph * up;
+        sines[((long)b * Fmax + t) * H1 + hm] = sinf(ph) * amp;
+    }
+    if (n == a_next) carry[hm] = cum;
+}
+
+// source_k reading the fixed sine_waves table at row b's own absolute sample offset, 480 W_b
+__global__ void source_slots_k(const float* __restrict__ f0, const float* __restrict__ sines, const float* __restrict__ noise,
+                               const float* __restrict__ lw, const float* __restrict__ lb, float* __restrict__ src,
+                               const int* __restrict__ frames, const int* __restrict__ tab, int Fmax, int H1, int up, float thr, float sigma, float amp) {
+    int b = blockIdx.y;
+    long n = blockIdx.x * 256L + threadIdx.x;
+    long S = (long)frames[b] * up;
+    if (n >= S) return;
+    const long n0 = (long)tab[b * SROW + SR_W] * up;
+    int t = (int)(n / up);
+    float f = f0[(long)b * Fmax + t];
+    float uv = f > thr ? 1.f : 0.f;
+    float namp = uv * sigma + ((1.f - uv) * amp) / 3.f;
+    float acc = lb[0];
+    for (int hm = 0; hm < H1; ++hm) {
+        float sw = sines[((long)b * Fmax + t) * H1 + hm] * uv + namp * noise[(n0 + n) * H1 + hm];
+        acc = fmaf(sw, lw[hm], acc);
+    }
+    src[(long)b * Fmax * up + n] = tanhf(acc);
+}
+
+// istft16_k writing samples [n_lo_b, s_out[b]) of row b's computed rows compact to wav[wav_row_b, 0 ..): the stream's new samples
+__global__ void istft16_slots_k(const float* __restrict__ spec, float* __restrict__ wav, const int* __restrict__ frames, const int* __restrict__ s_out,
+                                const int* __restrict__ tab, int Fmax, int spf, float limit, long wav_ld) {
+    int b = blockIdx.y;
+    const int n_lo = tab[b * SROW + SR_NLO];
+    long n = n_lo + blockIdx.x * 256L + threadIdx.x;
+    if (n >= s_out[b]) return;
+    int T = frames[b] * spf + 1;
+    int m = (int)n + 8;
+    int t_hi = min(m / 4, T - 1);
+    int t_lo = max((m - 15 + 3) / 4, 0);
+    float y = 0.f, env = 0.f;
+    for (int t = t_lo; t <= t_hi; ++t) {
+        int j = m - 4 * t;
+        const float* sp = spec + ((long)b * (Fmax * spf + 1) + t) * 18;
+        float v = sp[0] + ((j & 1) ? -sp[8] : sp[8]);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) {
+            int q = (k * j) & 15;
+            v += 2.f * (sp[k] * c_cos16[q] - sp[9 + k] * c_sin16[q]);
+        }
+        float w = c_hann16[j];
+        y += (v * (1.f / 16.f)) * w;
+        env += w * w;
+    }
+    y = y / env;
+    wav[tab[b * SROW + SR_WAVROW] * wav_ld + (n - n_lo)] = fminf(fmaxf(y, -limit), limit);
+}
+
 // ---- orchestration -----------------------------------------------------------------
 // Per-utterance row counts of every stage.  finalize (the whole utterance): everything follows F.  A streaming chunk
 // (finalize = false, generator.py:674-679, 708-709, 722-725; f0_predictor.py:98-99) spends its last frames as look-ahead
 // instead of zero padding: the f0 predictor's first conv takes 3 (F_f0 = F - 3 frames of f0 / source), conv_pre another 4
 // of those (F_dec = F - 7 decoder frames) and the last frame of samples is held back (S_out = 480 (F - 8)).
-static int set_lens(fy_hift* h, const int32_t* frames, int B, int Fmax, hipStream_t st, bool finalize = true) {
-    FY_CHECK(h && frames && B >= 1 && B <= h->max_batch && Fmax >= 1 && Fmax <= h->max_frames, FY_ERR_ARG,
+// fin_each (a stream-slot call, hift_infer_streams): finalize per row; the rows then share the handle's buffers at a pitch of Fmax
+// frames, so B * Fmax - not Fmax alone - is bounded by max_batch * max_frames.
+static int set_lens(fy_hift* h, const int32_t* frames, int B, int Fmax, hipStream_t st, bool finalize = true, const int32_t* fin_each = nullptr) {
+    FY_CHECK(h && frames && B >= 1 && B <= h->max_batch && Fmax >= 1 &&
+                 (fin_each ? (long)B * Fmax <= (long)h->max_batch * h->max_frames : Fmax <= h->max_frames), FY_ERR_ARG,
              "hift: batch %d / frames %d outside the handle's limits (%d, %d)", B, Fmax, h ? h->max_batch : 0, h ? h->max_frames : 0);
     const int look_f0 = h->w.f0c[0].KW - 1, look_pre = h->cfg.pre_look_right;
     std::vector<int> v(8 * h->max_batch, 0);
     for (int b = 0; b < B; ++b) {
         int F = frames[b];
+        if (fin_each) finalize = fin_each[b] != 0;
         FY_CHECK(F >= 1 && F <= Fmax, FY_ERR_ARG, "hift: frames[%d] = %d outside [1, %d]", b, F, Fmax);
         FY_CHECK(finalize || F >= look_f0 + look_pre + 2, FY_ERR_ARG, "hift: a streaming chunk needs at least %d frames (got %d)",
                  look_f0 + look_pre + 2, F);
@@ -468,39 +589,59 @@ static int run_conv(const ConvDesc& d, const ConvW& w, uint32_t flags, hipStream
 
 // L_pick: the length that picks the fp32 MFMA kernel's form (conv1d_f32_mfma: by L_out; the two forms sum the input channels in
 // different orders) - a window of an FY_INCREMENTAL call passes the whole call's, so its rows are summed as the whole call sums them
-static int hift_f0(fy_hift* h, int B, int Fmax, hipStream_t st, int L_pick = 0) {
+// B_mid / L_pick2 (a stream-slot call): the convs run once per form group - rows [0, B_mid) at L_pick (no row's whole length above
+// it), rows [B_mid, B) at L_pick2 - so every stream is summed as its own whole call sums it; the classifier is one launch.
+static int hift_f0(fy_hift* h, int B, int Fmax, hipStream_t st, int L_pick = 0, int B_mid = -1, int L_pick2 = 0) {
     const fy_hift_config& c = h->cfg;
-    const int* lF = h->lens;                               // mel frames
-    const int* lF0 = h->lens + 6 * h->max_batch;           // f0 frames (= mel frames unless a streaming chunk)
-    // condnet[0]: k4, 3 frames of right look-ahead; then 4x k3 left-causal; ELU after each (f0_predictor.py:74-90)
-    const float* in = h->mel_cl;
-    int in_ld = c.mel;
+    const bool groups = B_mid >= 0;
+    if (!groups) { B_mid = B; L_pick = std::max(Fmax, L_pick); }
     float* bufs[2] = {h->f0a, h->f0b};
-    for (int i = 0; i < 5; ++i) {
-        ConvDesc d = base_desc(B);
-        d.x = in; d.x_bs = (long)Fmax * in_ld; d.x_ld = in_ld; d.L_in = Fmax; d.in_len = i == 0 ? lF : lF0;
-        d.y = bufs[i & 1]; d.y_bs = (long)Fmax * c.f0_ch; d.y_ld = c.f0_ch; d.L_out = std::max(Fmax, L_pick); d.out_len = lF0;
-        d.Cin = i == 0 ? c.mel : c.f0_ch; d.Cout = c.f0_ch; d.KW = h->w.f0c[i].KW;
-        d.pad_left = i == 0 ? 0 : (d.KW - 1);
-        d.bias = h->w.f0c[i].bias; d.post_act = ACT_ELU;
-        FY_TRY(conv1d_f32_mfma(d, h->w.f0c[i], st));
-        in = bufs[i & 1]; in_ld = c.f0_ch;
+    for (int g = 0; g < 2; ++g) {
+        const int b0 = g ? B_mid : 0, nb = g ? B - B_mid : B_mid;
+        if (nb <= 0) continue;
+        const int* lF = h->lens + b0;                          // mel frames
+        const int* lF0 = h->lens + 6 * h->max_batch + b0;      // f0 frames (= mel frames unless a streaming chunk)
+        // condnet[0]: k4, 3 frames of right look-ahead; then 4x k3 left-causal; ELU after each (f0_predictor.py:74-90)
+        const float* in = h->mel_cl + (long)b0 * Fmax * c.mel;
+        int in_ld = c.mel;
+        for (int i = 0; i < 5; ++i) {
+            ConvDesc d = base_desc(nb);
+            float* out = bufs[i & 1] + (long)b0 * Fmax * c.f0_ch;
+            d.x = in; d.x_bs = (long)Fmax * in_ld; d.x_ld = in_ld; d.L_in = Fmax; d.in_len = i == 0 ? lF : lF0;
+            d.y = out; d.y_bs = (long)Fmax * c.f0_ch; d.y_ld = c.f0_ch; d.L_out = g ? L_pick2 : L_pick; d.out_len = lF0;
+            d.Cin = i == 0 ? c.mel : c.f0_ch; d.Cout = c.f0_ch; d.KW = h->w.f0c[i].KW;
+            d.pad_left = i == 0 ? 0 : (d.KW - 1);
+            d.bias = h->w.f0c[i].bias; d.post_act = ACT_ELU;
+            FY_TRY(conv1d_f32_mfma(d, h->w.f0c[i], st));
+            in = out; in_ld = c.f0_ch;
+        }
     }
-    hipLaunchKernelGGL(f0_classifier_k, dim3(cdiv(Fmax, 4), B), dim3(256), 0, st, in, h->cls_w, h->cls_b, h->f0, lF0, Fmax, c.f0_ch);
+    hipLaunchKernelGGL(f0_classifier_k, dim3(cdiv(Fmax, 4), B), dim3(256), 0, st, bufs[0], h->cls_w, h->cls_b, h->f0, h->lens + 6 * h->max_batch,
+                       Fmax, c.f0_ch);
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }
 
-// carry / a0 / a_next / n0: the FY_INCREMENTAL window (sine_phase_k, source_k); null / -1 / -1 / 0 for a whole call
+// carry / a0 / a_next / n0: the FY_INCREMENTAL window (sine_phase_k, source_k); null / -1 / -1 / 0 for a whole call.
+// tab (a stream-slot call): those values per batch row, the carries per slot in h->ss_phase
 static int hift_source(fy_hift* h, const float* f0, int B, int Fmax, const float* rand_ini, const float* sine_noise, hipStream_t st,
-                       double* carry = nullptr, int a0 = -1, int a_next = -1, long n0 = 0) {
+                       double* carry = nullptr, int a0 = -1, int a_next = -1, long n0 = 0, const int* tab = nullptr) {
     const fy_hift_config& c = h->cfg;
     (void)rand_ini;   // provably without effect on the output (see sine_phase_k); kept in the ABI for fidelity
     const int H1 = c.harmonics + 1;
-    hipLaunchKernelGGL(sine_phase_k, dim3(B), dim3(64), 0, st, f0, h->rad_phase, h->lens + 6 * h->max_batch, Fmax, H1, (float)c.sampling_rate,
-                       c.nsf_alpha, (float)h->up_total, carry, a0, a_next);
-    hipLaunchKernelGGL(source_k, dim3(cdiv(Fmax * h->up_total, 256), B), dim3(256), 0, st, f0, h->rad_phase, sine_noise, h->lin_w,
-                       h->lin_b, h->source, h->lens + 6 * h->max_batch, Fmax, H1, h->up_total, c.voiced_thr, c.nsf_sigma, c.nsf_alpha, n0);
+    const int* lF0 = h->lens + 6 * h->max_batch;
+    const dim3 sgrid(cdiv(Fmax * h->up_total, 256), B);
+    if (tab) {
+        hipLaunchKernelGGL(sine_phase_slots_k, dim3(B), dim3(64), 0, st, f0, h->rad_phase, lF0, tab, Fmax, H1, (float)c.sampling_rate,
+                           c.nsf_alpha, (float)h->up_total, h->ss_phase, h->ss_pitch);
+        hipLaunchKernelGGL(source_slots_k, sgrid, dim3(256), 0, st, f0, h->rad_phase, sine_noise, h->lin_w, h->lin_b, h->source, lF0, tab,
+                           Fmax, H1, h->up_total, c.voiced_thr, c.nsf_sigma, c.nsf_alpha);
+    } else {
+        hipLaunchKernelGGL(sine_phase_k, dim3(B), dim3(64), 0, st, f0, h->rad_phase, lF0, Fmax, H1, (float)c.sampling_rate,
+                           c.nsf_alpha, (float)h->up_total, carry, a0, a_next);
+        hipLaunchKernelGGL(source_k, sgrid, dim3(256), 0, st, f0, h->rad_phase, sine_noise, h->lin_w,
+                           h->lin_b, h->source, lF0, Fmax, H1, h->up_total, c.voiced_thr, c.nsf_sigma, c.nsf_alpha, n0);
+    }
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }
@@ -595,8 +736,10 @@ __global__ void reflect_row0_k(float* __restrict__ y, const float* __restrict__ 
         if (rs.ya[k]) rs.ya[k][(long)b * bs + c] = f32_to_bf16(snake_fast(v, rs.al[k][c]));
 }
 
-// n_lo / wav_off: the iSTFT writes samples [n_lo, S_out) of the rows computed, at wav + wav_off (FY_INCREMENTAL windows)
-static int hift_decode(fy_hift* h, int B, int Fmax, float* wav, uint32_t flags, hipStream_t st, int n_lo = 0, long wav_off = 0) {
+// n_lo / wav_off: the iSTFT writes samples [n_lo, S_out) of the rows computed, at wav + wav_off (FY_INCREMENTAL windows).
+// tab / wav_ld / max_new (a stream-slot call): n_lo per batch row; the rows' new samples, max_new at the most, go compact to wav (., wav_ld)
+static int hift_decode(fy_hift* h, int B, int Fmax, float* wav, uint32_t flags, hipStream_t st, int n_lo = 0, long wav_off = 0,
+                       const int* tab = nullptr, long wav_ld = 0, long max_new = 0) {
     const fy_hift_config& c = h->cfg;
     const int mb = h->max_batch;
     const int spf = h->stft_per_frame, up = h->up_total;
@@ -694,8 +837,12 @@ static int hift_decode(fy_hift* h, int B, int Fmax, float* wav, uint32_t flags, 
     }
     // the spectrum overwrites s_stft (no longer needed)
     hipLaunchKernelGGL(spec_k, dim3(cdiv(Tmax * 9, 256), B), dim3(256), 0, st, h->post, h->s_stft, h->lens + 7 * mb, Fmax, spf);
-    hipLaunchKernelGGL(istft16_k, dim3(cdiv(std::max(Fmax * up - n_lo, 1), 256), B), dim3(256), 0, st, h->s_stft, wav, h->lens + 7 * mb, h->lens + 5 * mb, Fmax, spf,
-                       c.audio_limit, n_lo, (long)Fmax * up, wav_off);
+    if (tab)
+        hipLaunchKernelGGL(istft16_slots_k, dim3(cdiv((int)std::max(max_new, 1L), 256), B), dim3(256), 0, st, h->s_stft, wav, h->lens + 7 * mb,
+                           h->lens + 5 * mb, tab, Fmax, spf, c.audio_limit, wav_ld);
+    else
+        hipLaunchKernelGGL(istft16_k, dim3(cdiv(std::max(Fmax * up - n_lo, 1), 256), B), dim3(256), 0, st, h->s_stft, wav, h->lens + 7 * mb, h->lens + 5 * mb, Fmax, spf,
+                           c.audio_limit, n_lo, (long)Fmax * up, wav_off);
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }
@@ -830,6 +977,141 @@ extern "C" int fy_hift_stream_reset(fy_hift* h) {
 extern "C" int fy_hift_stream_samples(const fy_hift* h) { return h ? (int)h->inc_samples : -1; }
 
 extern "C" int fy_hift_stream_window(const fy_hift* h) { return h ? h->inc_window : -1; }
+
+// ---- stream slots: the session and its call ------------------------------------------------------------------------------------------
+extern "C" int fy_hift_streams_close(fy_hift* h) {
+    FY_CHECK(h, FY_ERR_ARG, "fy_hift_streams_close: null handle");
+    if (h->ss_phase) (void)hipFree(h->ss_phase);
+    if (h->ss_tab) (void)hipFree(h->ss_tab);
+    h->ss_phase = nullptr; h->ss_tab = nullptr; h->ss_pitch = 0; h->ss_bytes = 0;
+    h->ss.clear();
+    return FY_OK;
+}
+
+extern "C" int fy_hift_streams_open(fy_hift* h, int32_t n_slots) {
+    FY_CHECK(h, FY_ERR_ARG, "fy_hift_streams_open: null handle");
+    FY_CHECK(n_slots >= 1 && n_slots <= h->max_batch, FY_ERR_ARG, "fy_hift_streams_open: %d slots outside [1, %d] (the handle's max_batch)",
+             n_slots, h->max_batch);
+    FY_TRY(fy_hift_streams_close(h));
+    const int pitch = (h->cfg.harmonics + 1 + 15) / 16 * 16;
+    const size_t pb = (size_t)n_slots * pitch * sizeof(double), tb = (size_t)n_slots * SROW * sizeof(int);
+    if (hipMalloc(&h->ss_phase, pb) != hipSuccess || hipMalloc(&h->ss_tab, tb) != hipSuccess) {
+        (void)hipGetLastError();
+        fy_hift_streams_close(h);
+        fy_set_error("fy_hift_streams_open: hipMalloc(%zu B) failed", pb + tb);
+        return FY_ERR_HIP;
+    }
+    h->ss_pitch = pitch; h->ss_bytes = pb + tb;
+    h->ss.assign(n_slots, fy_hift::Slot());      // (a slot's sums are read only after a call of the slot has stored them)
+    return FY_OK;
+}
+
+extern "C" int64_t fy_hift_streams_bytes(const fy_hift* h) { return h ? (int64_t)h->ss_bytes : 0; }
+
+extern "C" int fy_hift_stream_slot_reset(fy_hift* h, int32_t slot) {
+    FY_CHECK(h && slot >= 0 && slot < (int)h->ss.size(), FY_ERR_ARG, "fy_hift_stream_slot_reset: no slot %d (%d open)", slot, h ? (int)h->ss.size() : 0);
+    h->ss[slot] = fy_hift::Slot();
+    return FY_OK;
+}
+
+extern "C" int fy_hift_stream_slot_samples(const fy_hift* h, int32_t slot) {
+    return h && slot >= 0 && slot < (int)h->ss.size() ? (int)h->ss[slot].samples : -1;
+}
+
+extern "C" int fy_hift_stream_slot_window(const fy_hift* h, int32_t slot) {
+    return h && slot >= 0 && slot < (int)h->ss.size() ? h->ss[slot].window : -1;
+}
+
+extern "C" int fy_hift_infer_streams(fy_hift* h, const int32_t* slots, int32_t n, const float* const* mel, const int32_t* mel_ld,
+                                     const int32_t* frames, const int32_t* finalize, const float* rand_ini, const float* sine_noise, float* wav,
+                                     int32_t wav_ld, int32_t* n_new, uint32_t flags, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(h && slots && mel && mel_ld && frames && finalize && sine_noise && wav && n_new, FY_ERR_ARG, "fy_hift_infer_streams: null argument");
+    FY_CHECK(!h->ss.empty(), FY_ERR_ARG, "fy_hift_infer_streams: no stream-slot session is open (fy_hift_streams_open)");
+    FY_CHECK(!(flags & ~(FY_DIRECT | FY_PRECISE | FY_INCREMENTAL)), FY_ERR_ARG, "fy_hift_infer_streams: flags 0x%x (FY_DIRECT, FY_PRECISE or 0)", flags);
+    const int n_slots = (int)h->ss.size(), up = h->up_total, f0h = hift_f0_history(h);
+    const int min_chunk = (h->w.f0c[0].KW - 1) + h->cfg.pre_look_right + 2;
+    FY_CHECK(n >= 1 && n <= n_slots, FY_ERR_ARG, "fy_hift_infer_streams: %d streams in a session of %d slots", n, n_slots);
+    // the plan of every row, checked before any device work.  Rows are ordered by the form of the f0 convs their whole length
+    // selects (launch_f32_mfma: L_out <= 4096 or not), so each form group is a contiguous range of batch rows.
+    struct Row { int i, slot, W, Fw, a0, a_next, fin; long S_prev, S_out; };
+    std::vector<Row> rows;
+    std::vector<char> seen(n_slots, 0);
+    int Fmax = 0, L_pick[2] = {0, 0}, B_mid = 0;
+    long max_new = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n; ++i) {
+            if (pass == 0) {
+                const int s = slots[i];
+                FY_CHECK(s >= 0 && s < n_slots, FY_ERR_ARG, "fy_hift_infer_streams: slots[%d] = %d outside the session's %d slots", i, s, n_slots);
+                FY_CHECK(!seen[s], FY_ERR_ARG, "fy_hift_infer_streams: slot %d is listed twice", s);
+                seen[s] = 1;
+                FY_CHECK(mel[i] && frames[i] >= 1 && frames[i] <= mel_ld[i], FY_ERR_ARG, "fy_hift_infer_streams: frames[%d] = %d outside [1, %d] (mel_ld)",
+                         i, frames[i], mel_ld[i]);
+            }
+            if ((mel_ld[i] > 4096) != (pass == 1)) continue;
+            const fy_hift::Slot& sl = h->ss[slots[i]];
+            Row r;
+            r.i = i; r.slot = slots[i]; r.fin = finalize[i] != 0;
+            const int F = frames[i];
+            // continue the slot's stream, or start over (after a reset or a finalize call, or when the mel shrank)
+            r.S_prev = F >= sl.frames ? sl.samples : 0;
+            r.S_out = (long)(r.fin ? F : F - 8) * up;
+            // the slot's phase sums were added up from f0 values of the form its earlier calls ran (the two forms sum the input
+            // channels in different orders): a call on the other side of the switch runs from frame 0 - and still writes only the
+            // new samples - so that the sums are again those of the whole call at this length
+            const bool switched = r.S_prev > 0 && sl.big != (pass == 1);
+            r.W = switched ? 0 : (int)hift_window_start(h, r.S_prev);
+            r.Fw = F - r.W;
+            FY_CHECK(r.fin || r.Fw >= min_chunk, FY_ERR_ARG, "fy_hift_infer_streams: a streaming chunk needs at least %d frames (stream %d brings %d)",
+                     min_chunk, i, r.Fw);
+            FY_CHECK(r.S_out >= r.S_prev, FY_ERR_STATE, "fy_hift_infer_streams: stream %d ends before the samples already delivered", i);
+            r.a0 = r.W > 0 ? f0h : -1;
+            r.a_next = -1;
+            if (!r.fin) {
+                const long Wn = hift_window_start(h, r.S_out);
+                if (Wn > 0) r.a_next = (int)(Wn + f0h - r.W);
+                FY_CHECK(r.a_next < 0 || (r.a_next >= std::max(r.a0, 0) && r.a_next <= r.Fw - (h->w.f0c[0].KW - 1)), FY_ERR_STATE,
+                         "fy_hift_infer_streams: the next window's phase anchor %d of stream %d lies outside this call's exact f0 frames", r.a_next, i);
+            }
+            Fmax = std::max(Fmax, r.Fw);
+            max_new = std::max(max_new, r.S_out - r.S_prev);
+            L_pick[pass] = std::max(L_pick[pass], mel_ld[i]);
+            if (pass == 0) ++B_mid;
+            rows.push_back(r);
+        }
+    const long need_rows = (long)n * Fmax, have_rows = (long)h->max_batch * h->max_frames;
+    FY_CHECK(need_rows <= have_rows, FY_ERR_ARG, "fy_hift_infer_streams: %d streams x the longest window %d need %ld frame rows, the handle's buffers hold %ld",
+             n, Fmax, need_rows, have_rows);
+    FY_CHECK(wav_ld >= max_new, FY_ERR_ARG, "fy_hift_infer_streams: wav_ld %d is below the %ld new samples of the longest row", wav_ld, max_new);
+    std::vector<int> fw(n), fin(n), tab((size_t)n * SROW, 0);
+    for (int b = 0; b < n; ++b) {
+        const Row& r = rows[b];
+        fw[b] = r.Fw; fin[b] = r.fin;
+        int* t = tab.data() + (size_t)b * SROW;
+        const unsigned long long p = (unsigned long long)(uintptr_t)mel[r.i];
+        t[SR_SLOT] = r.slot; t[SR_W] = r.W; t[SR_LD] = mel_ld[r.i]; t[SR_A0] = r.a0; t[SR_ANEXT] = r.a_next;
+        t[SR_NLO] = (int)(r.S_prev - (long)r.W * up); t[SR_WAVROW] = r.i;
+        t[SR_MEL_LO] = (int)(unsigned)(p & 0xffffffffull); t[SR_MEL_HI] = (int)(unsigned)(p >> 32);
+        n_new[r.i] = (int)(r.S_out - r.S_prev);
+    }
+    FY_TRY(set_lens(h, fw.data(), n, Fmax, st, true, fin.data()));
+    FY_TRY(upload_ints(h->ss_tab, tab.data(), (int)tab.size(), st));
+    for (const Row& r : rows) h->ss[r.slot] = fy_hift::Slot();      // a call that fails below leaves no stream to continue in its slots
+    hipLaunchKernelGGL(mel_windows_k, dim3(cdiv(Fmax, 32), cdiv(h->cfg.mel, 32), n), dim3(256), 0, st, h->ss_tab, h->mel_cl, h->lens, h->cfg.mel, Fmax);
+    HIP_TRY(hipGetLastError());
+    FY_TRY(hift_f0(h, n, Fmax, st, L_pick[0], B_mid, L_pick[1]));
+    FY_TRY(hift_source(h, h->f0, n, Fmax, rand_ini, sine_noise, st, nullptr, -1, -1, 0, h->ss_tab));
+    FY_TRY(hift_decode(h, n, Fmax, wav, flags & ~FY_INCREMENTAL, st, 0, 0, h->ss_tab, wav_ld, max_new));
+    for (const Row& r : rows) {
+        fy_hift::Slot& sl = h->ss[r.slot];
+        sl.window = r.Fw;
+        sl.samples = r.fin ? 0 : r.S_out;
+        sl.frames = r.fin ? 0 : frames[r.i];
+        sl.big = mel_ld[r.i] > 4096;
+    }
+    return FY_OK;
+}
 
 extern "C" int fy_hift_f0(fy_hift* h, const float* mel, const int32_t* frames, int32_t B, int32_t Fmax, float* f0, void* stream) {
     hipStream_t st = (hipStream_t)stream;

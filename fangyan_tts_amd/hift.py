@@ -28,6 +28,12 @@ def _cfg_struct(cfg: HiftCfg) -> _lib.HiftConfig:
     return c
 
 
+def stream_new_samples(frames: int, finalize: bool, delivered: int, up: int = 480) -> int:
+    """Samples an incremental call brings: a chunk holds 8 frames back (3 + 4 of look-ahead and one of samples,
+    generator.py:713-726), the final call nothing; `delivered` are the stream's samples so far (0 on its first call)."""
+    return up * (frames if finalize else frames - 8) - delivered
+
+
 class HiftEngine:
     """Batched, ragged HiFT vocoder on one GPU.
 
@@ -101,6 +107,57 @@ class HiftEngine:
     def stream_window(self) -> int:
         """Mel frames the last incremental call ran through the network."""
         return int(_lib.lib().fy_hift_stream_window(self._h))
+
+    # ---- stream slots: several streams through one incremental pass (csrc/hift.hip: fy_hift_infer_streams)
+    def open_streams(self, n_slots: int):
+        """Give the handle `n_slots` (<= max_batch) incremental streams; the work buffers stay the handle's own."""
+        check(_lib.lib().fy_hift_streams_open(self._h, n_slots))
+
+    def close_streams(self):
+        check(_lib.lib().fy_hift_streams_close(self._h))
+
+    def streams_bytes(self) -> int:
+        """Device bytes of the open session (0: none)."""
+        return int(_lib.lib().fy_hift_streams_bytes(self._h))
+
+    def stream_slot_reset(self, slot: int):
+        check(_lib.lib().fy_hift_stream_slot_reset(self._h, slot))
+
+    def stream_slot_samples(self, slot: int) -> int:
+        """Samples the slot's stream has delivered (0: its next call computes everything; -1: no such slot)."""
+        return int(_lib.lib().fy_hift_stream_slot_samples(self._h, slot))
+
+    def stream_slot_window(self, slot: int) -> int:
+        """Mel frames of the slot's stream the last call ran through the network (-1: no such slot)."""
+        return int(_lib.lib().fy_hift_stream_slot_window(self._h, slot))
+
+    def inference_streams(self, slots: Sequence[int], mels: Sequence[torch.Tensor], rand_ini: torch.Tensor, sine_noise: torch.Tensor,
+                          finalize: Sequence[bool], flags: int = 0):
+        """Continue the streams of `slots` in one pass.  mels[i]: (1, 80, F_i) or (80, F_i), stream i's whole mel so far (separate
+        tensors of any lengths); finalize[i]: stream i's last call.  Returns a list of 1-D tensors, stream i's NEW samples
+        [stream_slot_samples(slots[i]) before the call, 480 (F_i - 8) or 480 F_i) - views of one (n, wav_ld) buffer - the same
+        values `inference(..., incremental=True)` writes there for that stream alone."""
+        n = len(slots)
+        assert n >= 1 and len(mels) == n and len(finalize) == n
+        ms = []
+        for m in mels:
+            m = m[0] if m.dim() == 3 else m
+            assert m.is_cuda and m.dtype == torch.float32 and m.dim() == 2 and m.shape[0] == self.cfg.mel
+            ms.append(m.contiguous())
+        frames = [int(m.shape[1]) for m in ms]
+        up = self.cfg.upsample_total
+        assert sine_noise.is_cuda and sine_noise.is_contiguous() and sine_noise.shape[-2] >= up * max(frames)
+        # what each slot has delivered; a slot given fewer frames than its last call (samples / up + 8) starts over, as in the library
+        done = [max(self.stream_slot_samples(s), 0) for s in slots]
+        done = [d if F >= d // up + 8 else 0 for d, F in zip(done, frames)]
+        wav_ld = max(1, max(stream_new_samples(F, bool(fin), d, up) for F, fin, d in zip(frames, finalize, done)))
+        wav = torch.zeros(n, wav_ld, device=self.device, dtype=torch.float32)
+        ptrs = (C.c_void_p * n)(*[m.data_ptr() for m in ms])
+        n_new = (C.c_int32 * n)()
+        check(_lib.lib().fy_hift_infer_streams(self._h, _lib.int_array(list(slots)), n, ptrs, _lib.int_array(frames), _lib.int_array(frames),
+                                               _lib.int_array([int(bool(f)) for f in finalize]), rand_ini.data_ptr(), sine_noise.data_ptr(),
+                                               wav.data_ptr(), wav_ld, n_new, flags, self._stream()))
+        return [wav[i, : n_new[i]] for i in range(n)]
 
     def f0(self, speech_feat, frames=None):
         mel, B, Fmax, fr = self._prep(speech_feat, frames)

@@ -133,6 +133,41 @@ int fy_hift_stream_samples(const fy_hift* h);
  * fixed margin - 37 frames for CosyVoice3's config) */
 int fy_hift_stream_window(const fy_hift* h);
 
+/* Stream slots: several stream=True utterances share one incremental vocoder pass.  A session gives the handle n_slots
+ * (1 .. max_batch) copies of what FY_INCREMENTAL keeps for its one stream - samples delivered, frames and window of the last call,
+ * and harmonics + 1 phase sums (doubles, device, a fixed pitch per slot) - and a small table for the per-row values of a call.  The
+ * handle's own work buffers are the session's: nothing else is allocated.  The single-stream state above is separate and
+ * untouched, and usable beside an open session.  Calls of a session are serial on one stream.  Opening again replaces the session;
+ * fy_hift_streams_close frees it; fy_hift_streams_bytes: the session's device bytes (0: none).
+ * fy_hift_stream_slot_reset / _samples / _window: per slot what fy_hift_stream_reset / _samples / _window are for the single
+ * stream (-1: no such slot).                                                                                                  */
+int fy_hift_streams_open(fy_hift* h, int32_t n_slots);
+int fy_hift_streams_close(fy_hift* h);
+int64_t fy_hift_streams_bytes(const fy_hift* h);
+int fy_hift_stream_slot_reset(fy_hift* h, int32_t slot);
+int fy_hift_stream_slot_samples(const fy_hift* h, int32_t slot);
+int fy_hift_stream_slot_window(const fy_hift* h, int32_t slot);
+/* Continue the streams in slots[0 .. n) (host int32, distinct) in ONE pass (the call implies FY_INCREMENTAL; flags: FY_DIRECT,
+ * FY_PRECISE or 0).  mel[n]: host array of device pointers - stream i's whole mel so far, (80, mel_ld[i]) fp32, valid in
+ * [0, frames[i]); the streams' mels are separate tensors of any lengths.  finalize[n] (host): per stream, nonzero = the
+ * stream's last call (no look-ahead frames, nothing held back), 0 = a streaming chunk as under FY_NO_FINALIZE.  wav: (n, wav_ld)
+ * fp32 - stream i's NEW samples [S_prev_i, S_out_i) land compact at row i from column 0, n_new[i] (host, out) of them; the rest
+ * of the row is left untouched.  rand_ini / sine_noise as for fy_hift_infer, sine_noise at least 480 * max frames[i] rows.
+ * Every slot follows FY_INCREMENTAL's rules on its own: its window starts a fixed margin before its S_prev; a slot after a reset,
+ * after a finalize call or given a shorter mel computes everything; a finalize call ends the slot's stream.  All listed streams
+ * go through every kernel together (B = n rows of max_i window_i frames): no launch is per stream, the per-row values travel
+ * as kernel arguments and the call does not wait on the host.  Only the fp32 f0 convolutions, whose form follows a stream's
+ * whole length (mel_ld[i] <= 4096 or not, as Fmax selects it in fy_hift_infer), run once per form present; the call that takes a
+ * stream across that length runs it from frame 0 (its phase sums came from the other form) and still writes only its new samples.
+ * The samples are bit for bit those fy_hift_infer writes at [S_prev_i, S_out_i) for stream i alone on its whole mel.
+ * FY_ERR_ARG (before any device work, the session as it was), with a message: no session open; a slot out of range or listed
+ * twice; n above the session's slots; frames[i] outside [1, mel_ld[i]]; a streaming chunk below the 9-frame minimum; n x the
+ * longest window above the handle's max_batch x max_frames frame rows; wav_ld below the largest n_new (the last two name the
+ * count needed).                                                                                                              */
+int fy_hift_infer_streams(fy_hift* h, const int32_t* slots, int32_t n, const float* const* mel, const int32_t* mel_ld,
+                          const int32_t* frames, const int32_t* finalize, const float* rand_ini, const float* sine_noise,
+                          float* wav, int32_t wav_ld, int32_t* n_new, uint32_t flags, void* stream);
+
 /* ============================ flow-matching decoder ============================
  * replaces CausalMaskedDiffWithDiT.inference(token, ..., prompt_feat, embedding, streaming, finalize=True)
  *   cosyvoice/flow/flow.py:358-403 (called from cli/model.py:418-427)                                   */
