@@ -109,6 +109,7 @@ def _declare(L):
     L.fy_flow_stream_rows.argtypes = [vp]
     L.fy_flow_streams_open.argtypes = [vp, i32, i32]
     L.fy_flow_streams_close.argtypes = [vp]
+    L.fy_flow_streams_precise.argtypes = [vp, i32]
     L.fy_flow_streams_bytes.argtypes = [vp]
     L.fy_flow_streams_bytes.restype = C.c_int64
     L.fy_flow_stream_slot_reset.argtypes = [vp, i32]

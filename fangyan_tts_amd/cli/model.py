@@ -13,6 +13,7 @@ from typing import Dict, Iterable, List, Optional, Sequence
 
 import torch
 
+from .._lib import FY_PRECISE
 from ..flow import FlowEngine
 from ..hift import HiftEngine
 from ..llm import LlmEngine
@@ -774,7 +775,7 @@ class CosyVoice3Model:
                 self._arm_lane_sampler(ln, self._next_batch_ids(), K)
                 out, _, _ = ln.llm.open_slots(self.max_tokens)
                 ln.llm.join(list(range(K)), text, ptext, pspeech)
-                ln.flow.open_streams(K, 2 * (self.max_tokens + self.max_prompt_tokens))
+                ln.flow.open_streams(K, 2 * (self.max_tokens + self.max_prompt_tokens), precise=bool(self.flow_flags & FY_PRECISE))
                 opened = True
                 # K <= self.max_batch (asserted above) <= ln.hift.max_batch (every lane's vocoder is built with at least max_batch
                 # rows), so K slots always fit; and a poll's n <= K windows of at most 2 * max_tokens frames fit its buffers

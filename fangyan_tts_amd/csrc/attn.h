@@ -22,6 +22,11 @@ int dit_attention_tab(const bf16_t* qkv, bf16_t* out, const DitSeqTab* tab, int 
 // three MFMAs per product keep the hi x hi, hi x lo and lo x hi terms, softmax in fp32.
 int dit_attention_split(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* out_hi, bf16_t* out_lo, const int* seq_len, int nseq, int Tmax, int H, int chunk,
                         hipStream_t st);
+// The per-sequence form of the split kernel, dit_attention_tab's addressing on both planes (the fp32-class incremental chunks and
+// stream slots).  The single stream's incremental call is two interleaved sequences: q_begin = T0, in_row = s, row_step = 2.  A
+// query's result is, bit for bit, what dit_attention_split gives for the same row and keys.
+int dit_attention_split_tab(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* out_hi, bf16_t* out_lo, const DitSeqTab* tab, int nseq, int Tmax, int H, int chunk,
+                            int row_step, hipStream_t st);
 
 // fp32 GQA attention over the KV cache, head_dim 64.  q: [R][q_ld]; K/V cache: [seq][Hk][max_ctx][64];
 // row r attends positions 0..row_pos[r] of sequence row_seq[r].

@@ -253,18 +253,33 @@ int dit_attention(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, 
 // query, the probabilities in registers are the B operand of the second product, V^T by ds_read_b64_tr_b16; K/V tiles of both
 // planes double-buffered in LDS (86 KB: one workgroup of up to 8 waves per CU, two waves per SIMD, Q fragments in registers).
 // qkv_hi / qkv_lo: bf16 [nseq*Tmax][3*H*64] as [q | k | v]; out_hi / out_lo: bf16 [nseq*Tmax][H*64]
-template <int AT_NW>
+// TAB (the incremental chunks and the stream slots of the fp32-class mode): seq_len is a table of DitSeqTab, as in dit_attention2_k -
+// per sequence its first query row, its length, the row of its frame 0 in the qkv planes and the output row of its first query;
+// frame t is row in_row + t * row_step.  Only the queries t >= q_begin are computed; a workgroup without one leaves at once, a wave
+// without one only helps staging.  A kept query still walks the 64-key tiles from key 0 in the whole-sequence launch's order, on
+// lane t % 32 of its wave, through the same masks, products and softmax: the bits of a row do not depend on the form, the grid or
+// the rows beside it.  TAB = false is the whole-sequence kernel as it was.
+template <int AT_NW, bool TAB = false>
 __global__ __launch_bounds__(AT_NW * 64) void dit_attention_split_k(const bf16_t* __restrict__ qkv_hi, const bf16_t* __restrict__ qkv_lo,
                                                                      bf16_t* __restrict__ out_hi, bf16_t* __restrict__ out_lo,
-                                                                     const int* __restrict__ seq_len, int Tmax, int H, int chunk, float scale_log2) {
+                                                                     const int* __restrict__ seq_len, int Tmax, int H, int chunk, float scale_log2, int row_step) {
     extern __shared__ __attribute__((aligned(16))) bf16_t at_smem[];
     constexpr int KSZ = 64 * AT_KP, VSZ = 64 * AT_VP, BUF = 2 * KSZ + 2 * VSZ;       // one buffer: K_hi, K_lo, V_hi, V_lo
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int s = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * (AT_NW * 32);
-    const int len = seq_len[s];
+    int len, q_begin = 0;
+    long in_row = 0, out_row = 0;
+    if constexpr (TAB) {
+        const int4 t = reinterpret_cast<const int4*>(seq_len)[s];
+        q_begin = t.x; len = t.y; in_row = t.z; out_row = t.w;
+    } else {
+        len = seq_len[s];
+    }
     if (q0 >= len) return;
-    const int ld = 3 * H * AT_D;
-    const long sbase = (long)s * Tmax * ld;
+    if constexpr (TAB) { if (q0 + AT_NW * 32 <= q_begin) return; }
+    const int ldq = 3 * H * AT_D;
+    const long ld = TAB ? (long)ldq * row_step : (long)ldq;                     // elements between two frames of the sequence
+    const long sbase = TAB ? in_row * ldq : (long)s * Tmax * ldq;
     const int lr = lane & 31, hf = lane >> 5;
     const int qrow = q0 + wid * 32 + lr;                     // this lane's query
     frag_ab qh[4], ql[4];                                    // B[k = 16ks + 8hf + j][col = query], both planes
@@ -311,7 +326,7 @@ __global__ __launch_bounds__(AT_NW * 64) void dit_attention_split_k(const bf16_t
     };
     const int gi = lane >> 4, li = lane & 15;
     const int v_off = (4 * hf + (li >> 2)) * AT_VP + 16 * (gi & 1) + 4 * (li & 3);
-    const bool wave_live = q0 + wid * 32 < len;              // a wave past the sequence end only helps staging
+    const bool wave_live = q0 + wid * 32 < len && (!TAB || q0 + wid * 32 + 32 > q_begin);      // a wave past the sequence end (TAB: or before the first wanted query) only helps staging
     load_kv(0);
     store_kv(0);
     __syncthreads();
@@ -394,8 +409,9 @@ __global__ __launch_bounds__(AT_NW * 64) void dit_attention_split_k(const bf16_t
         __syncthreads();
     }
     if (qrow >= len) return;
+    if constexpr (TAB) { if (qrow < q_begin) return; }
     const float inv = 1.f / l_run;
-    const long oo = ((long)s * Tmax + qrow) * (H * AT_D) + h * AT_D;
+    const long oo = (TAB ? out_row + (long)(qrow - q_begin) * row_step : (long)s * Tmax + qrow) * (H * AT_D) + h * AT_D;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -416,36 +432,49 @@ __global__ __launch_bounds__(AT_NW * 64) void dit_attention_split_k(const bf16_t
         }
 }
 
-template <int W>
+template <int W, bool TAB>
 static int dit_attention_split_launch(const bf16_t* qh, const bf16_t* ql, bf16_t* oh, bf16_t* ol, const int* seq_len, int nseq, int Tmax, int H, int chunk,
-                                      dim3 grid, hipStream_t st) {
+                                      int row_step, dim3 grid, hipStream_t st) {
     constexpr size_t lds = (size_t)2 * (2 * 64 * AT_KP + 2 * 64 * AT_VP) * sizeof(bf16_t);      // 86 016 B: above the 64 KB default
     // set once per device and kernel (several flow handles may make their first call at once: the setup is idempotent)
     static PerDeviceOnce attr_once;
     const int dslot = current_device_slot();
     if (!attr_once.done[dslot].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)dit_attention_split_k<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_TRY(hipFuncSetAttribute((const void*)dit_attention_split_k<W, TAB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_once.done[dslot].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((dit_attention_split_k<W>), grid, dim3(W * 64), lds, st, qh, ql, oh, ol, seq_len, Tmax, H, chunk, 0.125f * 1.4426950408889634f);
+    hipLaunchKernelGGL((dit_attention_split_k<W, TAB>), grid, dim3(W * 64), lds, st, qh, ql, oh, ol, seq_len, Tmax, H, chunk, 0.125f * 1.4426950408889634f, row_step);
     HIP_TRY(hipGetLastError());
     return FY_OK;
+}
+
+// 32 queries per wave, up to 8 waves per workgroup, the waves spread evenly over the workgroups of a (sequence, head); at least 4
+// (waves past the sequence end help staging the 4-plane K/V tiles).  Tmax: the longest sequence of the launch.
+template <bool TAB>
+static int dit_attention_split_any(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* out_hi, bf16_t* out_lo, const int* seq_len, int nseq, int Tmax, int H, int chunk,
+                                   int row_step, hipStream_t st) {
+    ProfScope prof("dit_attention_split", 0.0, st);
+    const int nw = cdiv(Tmax, 32), nblk = cdiv(nw, 8), W = std::max(4, cdiv(nw, nblk));
+    dim3 grid(cdiv(nw, W), H, nseq);
+    switch (W) {
+        case 4: return dit_attention_split_launch<4, TAB>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, row_step, grid, st);
+        case 5: return dit_attention_split_launch<5, TAB>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, row_step, grid, st);
+        case 6: return dit_attention_split_launch<6, TAB>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, row_step, grid, st);
+        case 7: return dit_attention_split_launch<7, TAB>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, row_step, grid, st);
+        default: return dit_attention_split_launch<8, TAB>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, row_step, grid, st);
+    }
 }
 
 int dit_attention_split(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* out_hi, bf16_t* out_lo, const int* seq_len, int nseq, int Tmax, int H, int chunk,
                         hipStream_t st) {
     FY_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && seq_len && nseq >= 1 && Tmax >= 1 && H >= 1, FY_ERR_ARG, "dit_attention_split: bad arguments");
-    // 32 queries per wave, up to 8 waves per workgroup, the waves spread evenly over the workgroups of a (sequence, head); at least 4
-    // (waves past the sequence end help staging the 4-plane K/V tiles)
-    const int nw = cdiv(Tmax, 32), nblk = cdiv(nw, 8), W = std::max(4, cdiv(nw, nblk));
-    dim3 grid(cdiv(nw, W), H, nseq);
-    switch (W) {
-        case 4: return dit_attention_split_launch<4>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, grid, st);
-        case 5: return dit_attention_split_launch<5>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, grid, st);
-        case 6: return dit_attention_split_launch<6>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, grid, st);
-        case 7: return dit_attention_split_launch<7>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, grid, st);
-        default: return dit_attention_split_launch<8>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, grid, st);
-    }
+    return dit_attention_split_any<false>(qkv_hi, qkv_lo, out_hi, out_lo, seq_len, nseq, Tmax, H, chunk, 1, st);
+}
+
+int dit_attention_split_tab(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* out_hi, bf16_t* out_lo, const DitSeqTab* tab, int nseq, int Tmax, int H, int chunk,
+                            int row_step, hipStream_t st) {
+    FY_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && tab && nseq >= 1 && Tmax >= 1 && H >= 1 && row_step >= 1, FY_ERR_ARG, "dit_attention_split_tab: bad arguments");
+    return dit_attention_split_any<true>(qkv_hi, qkv_lo, out_hi, out_lo, reinterpret_cast<const int*>(tab), nseq, Tmax, H, chunk, row_step, st);
 }
 
 // -----------------------------------------------------------------------------------------------

@@ -59,8 +59,11 @@ struct fy_flow {
     // incremental streaming (FY_INCREMENTAL, batch 1): the q | k | v rows of every (Euler step, block) as they were computed -
     // [n_steps][depth][2 Tmax][3 inner] bf16 - and the ODE state at every step, [(n_steps + 1)][Tmax][mel] fp32; inc_T = rows kept
     bf16_t* inc_qkv = nullptr;
+    bf16_t* inc_qkv_lo = nullptr;                       // the lo plane of the same rows, for streams kept in the fp32-class mode (first precise incremental call)
+    int* inc_tab = nullptr;                             // DitSeqTab [2]: the two interleaved sequences of the split attention's per-sequence form
     float* inc_x = nullptr;
     int inc_T = 0;
+    int inc_mode = 0;                                   // the arithmetic the kept rows were computed in (0 default, 1 FY_PRECISE): a call in the other one starts over
     int inc_np = -1, inc_npf = -1, inc_ntok = -1;       // the stream's prompt tokens / prompt frames / tokens at the last kept call (a cheap check that a call extends it)
     struct FlowStreams* ss = nullptr;                   // the stream-slot session (fy_flow_streams_open), or none
     ~fy_flow();
@@ -83,8 +86,12 @@ struct FlowStreams {
     int* tok_all = nullptr;
     float *emb = nullptr, *pre_a = nullptr, *mu_tok = nullptr, *spks = nullptr, *mu = nullptr, *cond = nullptr, *h = nullptr, *c1 = nullptr, *qf = nullptr, *v = nullptr;
     bf16_t *a_in = nullptr, *xn = nullptr, *ao = nullptr, *ff = nullptr;
+    // fp32-class mode (FY_PRECISE): the lo planes of the slot caches and of the work buffers, allocated together on the session's
+    // first precise call (all or nothing; counted in bytes from then on)
+    bf16_t *qkv_lo = nullptr, *a_in_lo = nullptr, *xn_lo = nullptr, *ao_lo = nullptr, *ff_lo = nullptr;
+    bool allow_precise = false;              // fy_flow_streams_precise: a session takes FY_PRECISE calls only once its owner has said so (they double its memory)
     std::vector<void*> ptrs;
-    struct Slot { int T = 0, np = -1, npf = -1, ntok = -1; };      // rows kept; prompt tokens / prompt frames / tokens at the last kept call
+    struct Slot { int T = 0, np = -1, npf = -1, ntok = -1, mode = 0; };      // rows kept; prompt tokens / prompt frames / tokens at the last kept call; its arithmetic (0 default, 1 FY_PRECISE)
     std::vector<Slot> slot;
     ~FlowStreams() { for (void* p : ptrs) (void)hipFree(p); }
 };
@@ -272,7 +279,7 @@ __global__ void stream_setup_k(const float* __restrict__ mu_tok, const float* __
 }
 // dit_assemble_k over the listed streams, x from the slots' state of this step
 __global__ void stream_assemble_k(const float* __restrict__ xs, const float* __restrict__ cond, const float* __restrict__ mu, const float* __restrict__ spks,
-                                  const int* __restrict__ stab, bf16_t* __restrict__ a, int Tp, int cap, int C) {
+                                  const int* __restrict__ stab, bf16_t* __restrict__ a, bf16_t* __restrict__ a_lo, int Tp, int cap, int C) {
     const int s = blockIdx.y, t = blockIdx.x, i = s >> 1, cfg = s & 1;
     const int k = threadIdx.x;               // 0 .. 4C
     if (k >= 4 * C) return;
@@ -283,7 +290,9 @@ __global__ void stream_assemble_k(const float* __restrict__ xs, const float* __r
         if (part == 0) v = xs[((long)stab[4 * i] * cap + t) * C + c];
         else if (!cfg) v = part == 1 ? cond[o + c] : (part == 2 ? mu[o + c] : spks[(long)i * C + c]);
     }
-    a[((long)s * Tp + t) * 4 * C + k] = f32_to_bf16(v);
+    const bf16_t hb = f32_to_bf16(v);
+    a[((long)s * Tp + t) * 4 * C + k] = hb;
+    if (a_lo) a_lo[((long)s * Tp + t) * 4 * C + k] = f32_to_bf16(v - bf16_to_f32(hb));      // fp32-class mode (FY_PRECISE): x = hi + lo
 }
 // the new rows of the residual stream, out of the front layout into the compact one
 __global__ __launch_bounds__(256) void stream_gather_k(const float* __restrict__ h, const int4* __restrict__ rows, float* __restrict__ out, int D) {
@@ -311,6 +320,30 @@ __global__ __launch_bounds__(256) void stream_qkv_store_k(const float* __restric
         pk.x = (uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16);
         pk.y = (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16);
         *reinterpret_cast<uint2*>(qkv + (long)rw.y * N + n) = pk;
+    }
+}
+// The fp32-class form: the same rotation on the fp32 sums, then x = hi + lo as two bf16 planes into the slot's slices of both caches -
+// what gemm_split's rotary epilogue (EPI 4) does with a row, on the sums its fp32 epilogue (EPI 2) stored
+__global__ __launch_bounds__(256) void stream_qkv_store_split_k(const float* __restrict__ qf, const int4* __restrict__ rows, const float2* __restrict__ rope,
+                                                                bf16_t* __restrict__ qkv, bf16_t* __restrict__ qkv_lo, int N, int rope_half, int rope_stride) {
+    const int r = blockIdx.x;
+    const int4 rw = rows[r];
+    for (int n = threadIdx.x * 4; n < N; n += 1024) {
+        float4 v = *reinterpret_cast<const float4*>(qf + (long)r * N + n);
+        const int nn = n >= rope_stride ? n - rope_stride : n;
+        if (n < 2 * rope_stride && nn < 2 * rope_half) {
+            const float2* tab = rope + (long)rw.z * rope_half + (nn >> 1);
+            const float2 c0 = tab[0], c1 = tab[1];
+            rope_rotate(v, make_float4(c0.x, c0.y, c1.x, c1.y));
+        }
+        const bf16_t h0 = f32_to_bf16(v.x), h1 = f32_to_bf16(v.y), h2 = f32_to_bf16(v.z), h3 = f32_to_bf16(v.w);
+        uint2 ph, pl;
+        ph.x = (uint32_t)h0 | ((uint32_t)h1 << 16);
+        ph.y = (uint32_t)h2 | ((uint32_t)h3 << 16);
+        pl.x = (uint32_t)f32_to_bf16(v.x - bf16_to_f32(h0)) | ((uint32_t)f32_to_bf16(v.y - bf16_to_f32(h1)) << 16);
+        pl.y = (uint32_t)f32_to_bf16(v.z - bf16_to_f32(h2)) | ((uint32_t)f32_to_bf16(v.w - bf16_to_f32(h3)) << 16);
+        *reinterpret_cast<uint2*>(qkv + (long)rw.y * N + n) = ph;
+        *reinterpret_cast<uint2*>(qkv_lo + (long)rw.y * N + n) = pl;
     }
 }
 // euler_k over the compact rows: the state of the next step from this step's, in the slots
@@ -767,15 +800,21 @@ static int dit_forward(fy_flow* f, int nseq, int Tmax, int slot, bool streaming,
 
 // the caches of the incremental streaming path, on first use: 2 x Tmax x 3 inner bf16 per (step, block) - 2.7 MB per frame row
 // of capacity at full size - and the ODE states; an allocation failure just means "not incremental"
-static int inc_alloc(fy_flow* f) {
-    if (f->inc_qkv && f->inc_x) return FY_OK;
+// (precise: also the lo plane of the q | k | v rows, the same bytes again - 5.4 MB per frame row in the fp32-class mode - on the
+// first precise incremental call)
+static int inc_alloc(fy_flow* f, bool precise) {
+    if (f->inc_qkv && f->inc_x && (!precise || (f->inc_qkv_lo && f->inc_tab))) return FY_OK;
     const fy_flow_config& c = f->cfg;
     const size_t nq = (size_t)c.n_timesteps * c.depth * 2 * f->Tmax * 3 * c.heads * c.head_dim, nx = (size_t)(c.n_timesteps + 1) * f->Tmax * c.mel;
+    const size_t need = (f->inc_qkv ? 0 : nq * 2) + (f->inc_x ? 0 : nx * 4) + (precise && !f->inc_qkv_lo ? nq * 2 : 0);
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < nq * 2 + nx * 4 + ((size_t)1 << 30)) return FY_ERR_HIP;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)1 << 30)) return FY_ERR_HIP;
+    const bool fresh = !f->inc_qkv || !f->inc_x;
     if (!f->inc_qkv && f->pool.alloc(&f->inc_qkv, nq) != FY_OK) return FY_ERR_HIP;
     if (!f->inc_x && f->pool.alloc(&f->inc_x, nx) != FY_OK) return FY_ERR_HIP;
-    f->inc_T = 0;
+    if (precise && !f->inc_qkv_lo && f->pool.alloc(&f->inc_qkv_lo, nq) != FY_OK) return FY_ERR_HIP;
+    if (precise && !f->inc_tab && f->pool.alloc(&f->inc_tab, (size_t)8) != FY_OK) return FY_ERR_HIP;
+    if (fresh) f->inc_T = 0;
     return FY_OK;
 }
 
@@ -787,13 +826,18 @@ static int inc_alloc(fy_flow* f) {
 // the qkv product of the new rows writes directly.  Under the chunk mask with T0 and T on chunk boundaries the frames before T0
 // see nothing of the new ones, so their keys, values and outputs are what the previous call computed: same bits as the full
 // recompute (tests/test_stream_gpu.py).
-static int dit_forward_inc(fy_flow* f, int step, int T0, int T, hipStream_t st) {
+// pr (FY_PRECISE): the same chain in dit_forward's split arithmetic - both planes of every operand, gemm_split with the handle's lo
+// weight planes, the split attention's per-sequence form (f->inc_tab) against both planes of the slice - row by row what
+// dit_forward(..., FY_PRECISE) runs: gemm_split has ONE tiling per shape whatever M is (128 x 128 ring tiles; the register-staged
+// 128-row kernel for the 80-column output projection), so a row's sums do not depend on M or on the rows beside it.
+static int dit_forward_inc(fy_flow* f, int step, int T0, int T, bool pr, hipStream_t st) {
     const fy_flow_config& c = f->cfg;
     const int D = c.dim, C = c.mel, inner = c.heads * c.head_dim, FF = D * c.ff_mult, nseq = 2, Mn = nseq * (T - T0);
     const size_t r0 = (size_t)nseq * T0;                                       // first new row
     GemmEpi e;
     e.bias = f->b_in; e.out = f->h; e.out_bf16 = 0; e.ldc = D;
-    FY_TRY(gemm_bf16(f->a_in, 4 * C, f->w_in, nseq * T, D, 4 * C, e, st));
+    if (pr) { e.a_lo = f->a_in_lo; e.w_lo = f->w_in_lo; e.gate_ones = f->ones; FY_TRY(gemm_split(f->a_in, 4 * C, f->w_in, nseq * T, D, 4 * C, e, st)); }
+    else FY_TRY(gemm_bf16(f->a_in, 4 * C, f->w_in, nseq * T, D, 4 * C, e, st));
     {
         ConvDesc d;
         memset(&d, 0, sizeof(d));
@@ -801,42 +845,54 @@ static int dit_forward_inc(fy_flow* f, int step, int T0, int T, hipStream_t st) 
         d.x = f->h; d.x_bs = D; d.x_ld = nseq * D; d.L_in = T; d.in_len = f->seq_len;          // sequence s = every second row from row s
         d.y = f->c1; d.y_bs = D; d.y_ld = nseq * D; d.L_out = T; d.out_len = f->seq_len;
         d.Cin = D; d.Cout = D; d.KW = c.conv_pos_k; d.pad_left = c.conv_pos_k - 1; d.bias = f->pos1.bias; d.post_act = ACT_MISH;
-        const bool mf = f->pos1.w_mfma != nullptr;
-        FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos1, false, st) : conv1d_f32_direct(d, f->pos1, st));
+        const bool mf = f->pos1.w_mfma != nullptr && !(pr && f->planes == 2);                  // dit_forward's rule
+        FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos1, pr, st) : conv1d_f32_direct(d, f->pos1, st));
         d.x = f->c1; d.y = f->h; d.bias = f->pos2.bias;
         d.add_resid = 1; d.resid = f->h; d.r_bs = D; d.r_ld = nseq * D;
-        FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos2, false, st) : conv1d_f32_direct(d, f->pos2, st));
+        FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos2, pr, st) : conv1d_f32_direct(d, f->pos2, st));
     }
     const float* modbase = f->mod + (size_t)step * c.depth * 6 * D;
     const size_t slice = (size_t)nseq * f->Tmax * 3 * inner;                 // one (step, block) slice of inc_qkv
     float* h = f->h + r0 * D;
     bf16_t* xn = f->xn + r0 * D;
+    bf16_t* const xn_lo = pr ? f->xn_lo + r0 * D : nullptr;
     for (int i = 0; i < c.depth; ++i) {
         const FlowBlockW& k = f->blk[i];
         const float* m = modbase + (size_t)i * 6 * D;
         bf16_t* qkv = f->inc_qkv + ((size_t)step * c.depth + i) * slice;
-        hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + D, m, xn, (bf16_t*)nullptr, Mn, D);
+        hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + D, m, xn, xn_lo, Mn, D);
         GemmEpi q;
         q.bias = k.bqkv; q.out = qkv + r0 * 3 * inner; q.out_bf16 = 1; q.ldc = 3 * inner;
         q.rope = f->rope + (size_t)T0 * (c.head_dim / 2); q.rope_T = T - T0; q.rope_div = nseq; q.rope_half = c.head_dim / 2; q.rope_stride = inner;
-        FY_TRY(gemm_bf16(xn, D, k.wqkv, Mn, 3 * inner, D, q, st));
-        FY_TRY(dit_attention(qkv, f->ao, f->seq_len, nseq, T, c.heads, c.static_chunk, st, T0, true));
+        if (pr) {
+            bf16_t* qkv_lo = f->inc_qkv_lo + ((size_t)step * c.depth + i) * slice;
+            q.a_lo = xn_lo; q.out_lo = qkv_lo + r0 * 3 * inner; q.w_lo = k.wqkv_lo;
+            FY_TRY(gemm_split(xn, D, k.wqkv, Mn, 3 * inner, D, q, st));
+            FY_TRY(dit_attention_split_tab(qkv, qkv_lo, f->ao, f->ao_lo, reinterpret_cast<const DitSeqTab*>(f->inc_tab), nseq, T, c.heads, c.static_chunk, nseq, st));
+        } else {
+            FY_TRY(gemm_bf16(xn, D, k.wqkv, Mn, 3 * inner, D, q, st));
+            FY_TRY(dit_attention(qkv, f->ao, f->seq_len, nseq, T, c.heads, c.static_chunk, st, T0, true));
+        }
         GemmEpi o;
         o.mode = EPI_GATE_RESID; o.bias = k.bo; o.resid = h; o.gate = m + 2 * D; o.ldc = D;
-        FY_TRY(gemm_bf16(f->ao + r0 * inner, inner, k.wo, Mn, D, inner, o, st));
-        hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + 4 * D, m + 3 * D, xn, (bf16_t*)nullptr, Mn, D);
+        if (pr) { o.a_lo = f->ao_lo + r0 * inner; o.w_lo = k.wo_lo; o.gate_ones = f->ones; FY_TRY(gemm_split(f->ao + r0 * inner, inner, k.wo, Mn, D, inner, o, st)); }
+        else FY_TRY(gemm_bf16(f->ao + r0 * inner, inner, k.wo, Mn, D, inner, o, st));
+        hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + 4 * D, m + 3 * D, xn, xn_lo, Mn, D);
         GemmEpi g;
         g.bias = k.b1; g.act = ACT_GELU_TANH; g.out = f->ff + r0 * FF; g.out_bf16 = 1; g.ldc = FF;
-        FY_TRY(gemm_bf16(xn, D, k.w1, Mn, FF, D, g, st));
+        if (pr) { g.a_lo = xn_lo; g.out_lo = f->ff_lo + r0 * FF; g.w_lo = k.w1_lo; FY_TRY(gemm_split(xn, D, k.w1, Mn, FF, D, g, st)); }
+        else FY_TRY(gemm_bf16(xn, D, k.w1, Mn, FF, D, g, st));
         GemmEpi r;
         r.mode = EPI_GATE_RESID; r.bias = k.b2; r.resid = h; r.gate = m + 5 * D; r.ldc = D;
-        FY_TRY(gemm_bf16(f->ff + r0 * FF, FF, k.w2, Mn, D, FF, r, st));
+        if (pr) { r.a_lo = f->ff_lo + r0 * FF; r.w_lo = k.w2_lo; r.gate_ones = f->ones; FY_TRY(gemm_split(f->ff + r0 * FF, FF, k.w2, Mn, D, FF, r, st)); }
+        else FY_TRY(gemm_bf16(f->ff + r0 * FF, FF, k.w2, Mn, D, FF, r, st));
     }
     const float* fn = f->fin + (size_t)step * 2 * D;
-    hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, fn, fn + D, xn, (bf16_t*)nullptr, Mn, D);
+    hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, fn, fn + D, xn, xn_lo, Mn, D);
     GemmEpi p;
     p.bias = f->b_out; p.out = f->v + r0 * C; p.out_bf16 = 0; p.ldc = C;
-    FY_TRY(gemm_bf16(xn, D, f->w_out, Mn, C, D, p, st));
+    if (pr) { p.a_lo = xn_lo; p.w_lo = f->w_out_lo; p.gate_ones = f->ones; FY_TRY(gemm_split(xn, D, f->w_out, Mn, C, D, p, st)); }
+    else FY_TRY(gemm_bf16(xn, D, f->w_out, Mn, C, D, p, st));
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }
@@ -909,24 +965,31 @@ extern "C" int fy_flow_infer(fy_flow* f, const int32_t* token, int32_t tok_ld, c
     hipLaunchKernelGGL(flow_setup_k, dim3(Tmax, B), dim3(128), 0, st, f->mu_tok, prompt_feat, (long)pfeat_rows * C, rand_noise, noise_ld, d_T,
                        d_pmel, f->mu, f->cond, f->x, Tmax, Nmax, C);
     if (flags & FY_PRECISE) FY_TRY(ensure_precise(f));
-    // FY_INCREMENTAL (a streaming chunk at batch 1, bf16 mode): T0 = rows the previous call of this stream left (0: none, or not on
-    // a chunk boundary - everything is computed, and kept for the next call)
-    const bool inc = (flags & FY_INCREMENTAL) && B == 1 && (flags & FY_STREAMING) && (flags & FY_NO_FINALIZE) && !(flags & (FY_PRECISE | FY_DIRECT)) &&
-                     c.static_chunk > 0 && Tmax % c.static_chunk == 0 && inc_alloc(f) == FY_OK;
+    // FY_INCREMENTAL (a streaming chunk at batch 1, default or fp32-class arithmetic; not FY_DIRECT): T0 = rows the previous call of
+    // this stream left (0: none, or not on a chunk boundary - everything is computed, and kept for the next call)
+    const bool pr = (flags & FY_PRECISE) != 0;
+    const bool inc = (flags & FY_INCREMENTAL) && B == 1 && (flags & FY_STREAMING) && (flags & FY_NO_FINALIZE) && !(flags & FY_DIRECT) &&
+                     c.static_chunk > 0 && Tmax % c.static_chunk == 0 && inc_alloc(f, pr) == FY_OK;
     if (inc) {
         int T0 = f->inc_T;
         if (T0 % c.static_chunk != 0 || T0 >= Tmax) T0 = 0;
+        if (f->inc_mode != (pr ? 1 : 0)) T0 = 0;           // the kept rows are the other arithmetic's: a stream never mixes the two
+        f->inc_mode = pr ? 1 : 0;
         // a call extends the stream only with the same prompt and at least the tokens it had (a caller that forgot fy_flow_stream_reset
         // between two utterances would otherwise attend the previous utterance's keys): anything else starts over
         if (n_prompt[0] != f->inc_np || n_pfeat[0] != f->inc_npf || n_token[0] < f->inc_ntok) T0 = 0;
         f->inc_np = n_prompt[0]; f->inc_npf = n_pfeat[0]; f->inc_ntok = n_token[0];
+        if (pr) {                                          // (T0 is final here: the table and dit_forward_inc must agree on it)
+            const int tab[8] = {T0, Tmax, 0, 2 * T0, T0, Tmax, 1, 2 * T0 + 1};       // DitSeqTab of the two interleaved sequences
+            FY_TRY(upload_ints(f->inc_tab, tab, 8, st));
+        }
         float* xs = f->inc_x;
         const size_t xslice = (size_t)f->Tmax * C;
         for (int step = 0; step < c.n_timesteps; ++step) {
             // the state at this step: the earlier rows as the previous calls left them, the new rows as they evolve in f->x
             HIP_TRY(hipMemcpyAsync(xs + step * xslice + (size_t)T0 * C, f->x + (size_t)T0 * C, (size_t)(Tmax - T0) * C * sizeof(float), hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(dit_assemble_k, dim3(Tmax, 2), dim3(4 * C), 0, st, xs + step * xslice, f->cond, f->mu, f->spks, d_T, f->a_in, (bf16_t*)nullptr, Tmax, C, 1, 2);
-            FY_TRY(dit_forward_inc(f, step, T0, Tmax, st));
+            hipLaunchKernelGGL(dit_assemble_k, dim3(Tmax, 2), dim3(4 * C), 0, st, xs + step * xslice, f->cond, f->mu, f->spks, d_T, f->a_in, pr ? f->a_in_lo : (bf16_t*)nullptr, Tmax, C, 1, 2);
+            FY_TRY(dit_forward_inc(f, step, T0, Tmax, pr, st));
             hipLaunchKernelGGL(euler_k, dim3(Tmax - T0, 1), dim3(128), 0, st, f->x, f->v, d_T, Tmax, C, f->dt_of_step[step], c.cfg_rate, T0, 1);
         }
         HIP_TRY(hipMemcpyAsync(xs + c.n_timesteps * xslice + (size_t)T0 * C, f->x + (size_t)T0 * C, (size_t)(Tmax - T0) * C * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1004,6 +1067,45 @@ extern "C" int fy_flow_streams_open(fy_flow* f, int32_t n_slots, int32_t cap_fra
 
 extern "C" int64_t fy_flow_streams_bytes(const fy_flow* f) { return f && f->ss ? (int64_t)f->ss->bytes : 0; }
 
+// A session as opened takes the default arithmetic only, as it always has: FY_PRECISE on it is an argument error.  Its owner enables
+// the fp32-class mode for it here (nothing is allocated yet); disabling again keeps whatever lo planes exist until close.
+extern "C" int fy_flow_streams_precise(fy_flow* f, int32_t enable) {
+    FY_CHECK(f, FY_ERR_ARG, "fy_flow_streams_precise: null handle");
+    FY_CHECK(f->ss, FY_ERR_STATE, "fy_flow_streams_precise: no stream-slot session (fy_flow_streams_open)");
+    f->ss->allow_precise = enable != 0;
+    return FY_OK;
+}
+
+// The session's lo planes (FY_PRECISE), on its first precise call: the slot caches a second time and the lo planes of the work
+// buffers.  Everything or nothing: on a failure the call fails with the byte count and the session stays as it was, usable in the
+// default mode.
+static int streams_ensure_precise(fy_flow* f) {
+    FlowStreams& S = *f->ss;
+    if (S.qkv_lo) return FY_OK;
+    const fy_flow_config& c = f->cfg;
+    const size_t D = c.dim, C = c.mel, inner = (size_t)c.heads * c.head_dim, FF = D * c.ff_mult, R = (size_t)2 * S.n_slots * S.cap;
+    const size_t n_qkv = (size_t)c.n_timesteps * c.depth * R * 3 * inner;
+    const size_t need = (n_qkv + R * (4 * C + D + inner + FF)) * sizeof(bf16_t);      // (as fy_flow_streams_open counts: without each buffer's 256 bytes of tail padding)
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    FY_CHECK(need + ((size_t)1 << 30) <= free_b, FY_ERR_HIP, "fy_flow_infer_streams: the lo planes of %d slots of %d frames (FY_PRECISE) need %zu bytes, %zu are free",
+             S.n_slots, S.cap, need, free_b);
+    const size_t counts[5] = {n_qkv, R * 4 * C, R * D, R * inner, R * FF};
+    void* got[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 5; ++i) {
+        hipError_t e = hipMalloc(&got[i], counts[i] * sizeof(bf16_t) + 256);
+        if (e != hipSuccess) {
+            for (int j = 0; j < i; ++j) (void)hipFree(got[j]);
+            fy_set_error("fy_flow_infer_streams: hipMalloc(%zu B) of the %zu bytes of lo planes (FY_PRECISE) failed: %s", counts[i] * sizeof(bf16_t), need, hipGetErrorString(e));
+            return FY_ERR_HIP;
+        }
+    }
+    for (int i = 0; i < 5; ++i) S.ptrs.push_back(got[i]);
+    S.qkv_lo = (bf16_t*)got[0]; S.a_in_lo = (bf16_t*)got[1]; S.xn_lo = (bf16_t*)got[2]; S.ao_lo = (bf16_t*)got[3]; S.ff_lo = (bf16_t*)got[4];
+    S.bytes += need;
+    return FY_OK;
+}
+
 extern "C" int fy_flow_stream_slot_reset(fy_flow* f, int32_t slot) {
     FY_CHECK(f, FY_ERR_ARG, "fy_flow_stream_slot_reset: null handle");
     FY_CHECK(f->ss, FY_ERR_STATE, "fy_flow_stream_slot_reset: no stream-slot session (fy_flow_streams_open)");
@@ -1022,6 +1124,9 @@ extern "C" int fy_flow_stream_slot_rows(const fy_flow* f, int32_t slot) {
 // paid once for the call: per block one LayerNorm-modulate, one product each for qkv, out-projection, ff1 and ff2 over
 // sum_i 2 (T_i - T0_i) rows, one attention launch over the 2 n sequences (per-sequence table), and one launch that rotates and
 // stores the q | k | v rows into their slots.  Nothing inside the (step, block) loops is issued per stream.
+// FY_PRECISE: the same chain in the split arithmetic (both planes of every operand and of the caches, gemm_split, the split
+// attention's per-sequence form); each slot records the arithmetic its rows were kept in, and a slot continued in the other one is
+// recomputed in full while its neighbours extend.
 extern "C" int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n, const int32_t* token, int32_t tok_ld, const int32_t* n_token,
                                      const int32_t* prompt_token, int32_t ptok_ld, const int32_t* n_prompt, const float* prompt_feat, int32_t pfeat_rows,
                                      const int32_t* n_pfeat, const float* embedding, const float* rand_noise, int32_t noise_ld, float* mel,
@@ -1032,8 +1137,10 @@ extern "C" int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n
     FlowStreams& S = *f->ss;
     const fy_flow_config& c = f->cfg;
     FY_CHECK(n >= 1 && n <= S.n_slots, FY_ERR_ARG, "fy_flow_infer_streams: %d streams outside [1, %d]", n, S.n_slots);
-    FY_CHECK((flags & FY_STREAMING) && (flags & FY_NO_FINALIZE) && !(flags & (FY_PRECISE | FY_DIRECT)), FY_ERR_ARG,
-             "fy_flow_infer_streams: needs FY_STREAMING | FY_NO_FINALIZE and the default arithmetic (flags %u)", flags);
+    FY_CHECK((flags & FY_STREAMING) && (flags & FY_NO_FINALIZE), FY_ERR_ARG, "fy_flow_infer_streams: needs FY_STREAMING | FY_NO_FINALIZE (flags %u)", flags);
+    FY_CHECK(!(flags & FY_DIRECT), FY_ERR_ARG, "fy_flow_infer_streams: FY_DIRECT has no incremental form - the default arithmetic or FY_PRECISE (flags %u)", flags);
+    const bool pr = (flags & FY_PRECISE) != 0;
+    FY_CHECK(!pr || S.allow_precise, FY_ERR_ARG, "fy_flow_infer_streams: FY_PRECISE on a session that was not enabled for it (fy_flow_streams_precise) (flags %u)", flags);
     const int C = c.mel, D = c.dim, inner = c.heads * c.head_dim, FF = D * c.ff_mult, ns = S.n_slots, cap = S.cap, look = c.pre_lookahead, chunk = c.static_chunk;
     std::vector<int> tab(19 * ns, 0), T0s(n), Ts(n);
     int* h_atab = tab.data();
@@ -1055,6 +1162,7 @@ extern "C" int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n
         int T0 = sl.T;
         if (T % chunk != 0 || T0 % chunk != 0 || T0 >= T) T0 = 0;
         if (n_prompt[i] != sl.np || n_pfeat[i] != sl.npf || n_token[i] < sl.ntok) T0 = 0;
+        if (sl.mode != (pr ? 1 : 0)) T0 = 0;            // kept in the other arithmetic: this slot is recomputed in full, its neighbours are not
         T0s[i] = T0; Ts[i] = T;
         h_len[0 * ns + i] = n_all; h_len[1 * ns + i] = T; h_len[2 * ns + i] = n_pfeat[i]; h_len[3 * ns + i] = n_prompt[i]; h_len[4 * ns + i] = n_all - look;
         h_sl[2 * i] = h_sl[2 * i + 1] = T;
@@ -1066,9 +1174,10 @@ extern "C" int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n
         Mn += 2 * (T - T0);
         Tp = std::max(Tp, T); Nmax = std::max(Nmax, n_all);
     }
+    if (pr) FY_TRY(streams_ensure_precise(f));          // (nothing launched yet, the slots' records as they were)
     for (int i = 0; i < n; ++i) {                       // past the checks: the call will run, the slots' records move
         FlowStreams::Slot& sl = S.slot[slots[i]];
-        sl.np = n_prompt[i]; sl.npf = n_pfeat[i]; sl.ntok = n_token[i];
+        sl.np = n_prompt[i]; sl.npf = n_pfeat[i]; sl.ntok = n_token[i]; sl.mode = pr ? 1 : 0;
         sl.T = Ts[i] % chunk == 0 ? Ts[i] : 0;          // a stream that ends off a chunk boundary keeps nothing a later call could extend
     }
     FY_TRY(upload_ints(S.tab, tab.data(), (int)tab.size(), st));
@@ -1081,13 +1190,15 @@ extern "C" int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n
     hipLaunchKernelGGL(stream_setup_k, dim3(Tp, n), dim3(128), 0, st, S.mu_tok, prompt_feat, (long)pfeat_rows * C, rand_noise, noise_ld, d_stab, d_pmel,
                        S.mu, S.cond, S.xs, Tp, Nmax, cap, C);
     const int nseq = 2 * n, Mf = nseq * Tp;
-    const bool mf = f->pos1.w_mfma != nullptr;
+    const bool mf = f->pos1.w_mfma != nullptr && !(pr && f->planes == 2);     // dit_forward's rule
+    bf16_t* const xn_lo = pr ? S.xn_lo : nullptr;
     for (int step = 0; step < c.n_timesteps; ++step) {
         const float* xs = S.xs + step * xslice;
-        hipLaunchKernelGGL(stream_assemble_k, dim3(Tp, nseq), dim3(4 * C), 0, st, xs, S.cond, S.mu, S.spks, d_stab, S.a_in, Tp, cap, C);
+        hipLaunchKernelGGL(stream_assemble_k, dim3(Tp, nseq), dim3(4 * C), 0, st, xs, S.cond, S.mu, S.spks, d_stab, S.a_in, pr ? S.a_in_lo : (bf16_t*)nullptr, Tp, cap, C);
         GemmEpi e;
         e.bias = f->b_in; e.out = S.h; e.out_bf16 = 0; e.ldc = D;
-        FY_TRY(gemm_bf16(S.a_in, 4 * C, f->w_in, Mf, D, 4 * C, e, st));
+        if (pr) { e.a_lo = S.a_in_lo; e.w_lo = f->w_in_lo; e.gate_ones = f->ones; FY_TRY(gemm_split(S.a_in, 4 * C, f->w_in, Mf, D, 4 * C, e, st)); }
+        else FY_TRY(gemm_bf16(S.a_in, 4 * C, f->w_in, Mf, D, 4 * C, e, st));
         {
             ConvDesc d;
             memset(&d, 0, sizeof(d));
@@ -1095,10 +1206,10 @@ extern "C" int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n
             d.x = S.h; d.x_bs = (long)Tp * D; d.x_ld = D; d.L_in = Tp; d.in_len = d_sl;
             d.y = S.c1; d.y_bs = (long)Tp * D; d.y_ld = D; d.L_out = Tp; d.out_len = d_sl;
             d.Cin = D; d.Cout = D; d.KW = c.conv_pos_k; d.pad_left = c.conv_pos_k - 1; d.bias = f->pos1.bias; d.post_act = ACT_MISH;
-            FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos1, false, st) : conv1d_f32_direct(d, f->pos1, st));
+            FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos1, pr, st) : conv1d_f32_direct(d, f->pos1, st));
             d.x = S.c1; d.y = S.h; d.bias = f->pos2.bias;
             d.add_resid = 1; d.resid = S.h; d.r_bs = (long)Tp * D; d.r_ld = D;
-            FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos2, false, st) : conv1d_f32_direct(d, f->pos2, st));
+            FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos2, pr, st) : conv1d_f32_direct(d, f->pos2, st));
         }
         float* h = S.c1;                                 // the compact residual stream
         hipLaunchKernelGGL(stream_gather_k, dim3(Mn), dim3(256), 0, st, S.h, S.rows, h, D);
@@ -1107,28 +1218,41 @@ extern "C" int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n
             const FlowBlockW& k = f->blk[i];
             const float* m = modbase + (size_t)i * 6 * D;
             bf16_t* qkv = S.qkv + ((size_t)step * c.depth + i) * qslice;
-            hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + D, m, S.xn, (bf16_t*)nullptr, Mn, D);
+            hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + D, m, S.xn, xn_lo, Mn, D);
             GemmEpi q;
             q.bias = k.bqkv; q.out = S.qf; q.out_bf16 = 0; q.ldc = 3 * inner;
-            FY_TRY(gemm_bf16(S.xn, D, k.wqkv, Mn, 3 * inner, D, q, st));
-            hipLaunchKernelGGL(stream_qkv_store_k, dim3(Mn), dim3(256), 0, st, S.qf, S.rows, f->rope, qkv, 3 * inner, c.head_dim / 2, inner);
-            FY_TRY(dit_attention_tab(qkv, S.ao, d_atab, nseq, Tp, c.heads, chunk, 2, st));
+            if (pr) {
+                // the fp32 sums of the split product (its fp32 epilogue), then rotation + split into both planes of the slots' slices
+                bf16_t* qkv_lo = S.qkv_lo + ((size_t)step * c.depth + i) * qslice;
+                q.a_lo = xn_lo; q.w_lo = k.wqkv_lo; q.gate_ones = f->ones;
+                FY_TRY(gemm_split(S.xn, D, k.wqkv, Mn, 3 * inner, D, q, st));
+                hipLaunchKernelGGL(stream_qkv_store_split_k, dim3(Mn), dim3(256), 0, st, S.qf, S.rows, f->rope, qkv, qkv_lo, 3 * inner, c.head_dim / 2, inner);
+                FY_TRY(dit_attention_split_tab(qkv, qkv_lo, S.ao, S.ao_lo, d_atab, nseq, Tp, c.heads, chunk, 2, st));
+            } else {
+                FY_TRY(gemm_bf16(S.xn, D, k.wqkv, Mn, 3 * inner, D, q, st));
+                hipLaunchKernelGGL(stream_qkv_store_k, dim3(Mn), dim3(256), 0, st, S.qf, S.rows, f->rope, qkv, 3 * inner, c.head_dim / 2, inner);
+                FY_TRY(dit_attention_tab(qkv, S.ao, d_atab, nseq, Tp, c.heads, chunk, 2, st));
+            }
             GemmEpi o;
             o.mode = EPI_GATE_RESID; o.bias = k.bo; o.resid = h; o.gate = m + 2 * D; o.ldc = D;
-            FY_TRY(gemm_bf16(S.ao, inner, k.wo, Mn, D, inner, o, st));
-            hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + 4 * D, m + 3 * D, S.xn, (bf16_t*)nullptr, Mn, D);
+            if (pr) { o.a_lo = S.ao_lo; o.w_lo = k.wo_lo; o.gate_ones = f->ones; FY_TRY(gemm_split(S.ao, inner, k.wo, Mn, D, inner, o, st)); }
+            else FY_TRY(gemm_bf16(S.ao, inner, k.wo, Mn, D, inner, o, st));
+            hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, m + 4 * D, m + 3 * D, S.xn, xn_lo, Mn, D);
             GemmEpi g;
             g.bias = k.b1; g.act = ACT_GELU_TANH; g.out = S.ff; g.out_bf16 = 1; g.ldc = FF;
-            FY_TRY(gemm_bf16(S.xn, D, k.w1, Mn, FF, D, g, st));
+            if (pr) { g.a_lo = xn_lo; g.out_lo = S.ff_lo; g.w_lo = k.w1_lo; FY_TRY(gemm_split(S.xn, D, k.w1, Mn, FF, D, g, st)); }
+            else FY_TRY(gemm_bf16(S.xn, D, k.w1, Mn, FF, D, g, st));
             GemmEpi r;
             r.mode = EPI_GATE_RESID; r.bias = k.b2; r.resid = h; r.gate = m + 5 * D; r.ldc = D;
-            FY_TRY(gemm_bf16(S.ff, FF, k.w2, Mn, D, FF, r, st));
+            if (pr) { r.a_lo = S.ff_lo; r.w_lo = k.w2_lo; r.gate_ones = f->ones; FY_TRY(gemm_split(S.ff, FF, k.w2, Mn, D, FF, r, st)); }
+            else FY_TRY(gemm_bf16(S.ff, FF, k.w2, Mn, D, FF, r, st));
         }
         const float* fn = f->fin + (size_t)step * 2 * D;
-        hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, fn, fn + D, S.xn, (bf16_t*)nullptr, Mn, D);
+        hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mn, 4)), dim3(256), 0, st, h, fn, fn + D, S.xn, xn_lo, Mn, D);
         GemmEpi p;
         p.bias = f->b_out; p.out = S.v; p.out_bf16 = 0; p.ldc = C;
-        FY_TRY(gemm_bf16(S.xn, D, f->w_out, Mn, C, D, p, st));
+        if (pr) { p.a_lo = xn_lo; p.w_lo = f->w_out_lo; p.gate_ones = f->ones; FY_TRY(gemm_split(S.xn, D, f->w_out, Mn, C, D, p, st)); }
+        else FY_TRY(gemm_bf16(S.xn, D, f->w_out, Mn, C, D, p, st));
         hipLaunchKernelGGL(stream_euler_k, dim3(Mn / 2), dim3(128), 0, st, xs, S.xs + (step + 1) * xslice, S.v, S.rows, cap, C, f->dt_of_step[step], c.cfg_rate);
     }
     const float* xe = S.xs + c.n_timesteps * xslice;

@@ -114,7 +114,9 @@ class FlowEngine:
         streaming / finalize as in the reference (flow.py:358-403): the chunk attention mask, and the last
         pre_lookahead tokens as look-ahead context only (valid frames 2*(n_token[b] - pre_lookahead)).
         incremental (with streaming, finalize=False, one utterance): this call extends the previous incremental call of the handle -
-        only the new rows go through the DiT blocks (FY_INCREMENTAL; `stream_reset` starts a new stream).  Same result."""
+        only the new rows go through the DiT blocks (FY_INCREMENTAL; `stream_reset` starts a new stream).  Same result.  Works in
+        the default arithmetic and with flags=FY_PRECISE (a call in the other arithmetic than the kept rows' starts over); with
+        FY_DIRECT the call is computed whole."""
         if incremental:
             flags |= _lib.FY_INCREMENTAL
         if streaming:
@@ -155,18 +157,22 @@ class FlowEngine:
         return int(_lib.lib().fy_flow_stream_rows(self._h))
 
     # ---- stream slots: several stream=True utterances share one chunk pass (include/fy_cosy3.h) ----
-    def open_streams(self, n_slots: int, cap_frames: int):
+    def open_streams(self, n_slots: int, cap_frames: int, precise: bool = False):
         """A session of n_slots incremental caches of cap_frames mel rows (prompt + generated) each; raises FyError when the
-        device does not have the memory (2.7 MB per frame row and slot at full size)."""
+        device does not have the memory (2.7 MB per frame row and slot at full size).  precise: the session also takes
+        `inference_streams(..., flags=FY_PRECISE)` (its first such call allocates the lo planes, the same bytes again); a session
+        opened without it refuses that flag, as it always has."""
         with torch.cuda.device(self.device):
             check(_lib.lib().fy_flow_streams_open(self._h, n_slots, cap_frames))
+            if precise:
+                check(_lib.lib().fy_flow_streams_precise(self._h, 1))
 
     def close_streams(self):
         check(_lib.lib().fy_flow_streams_close(self._h))
 
     @property
     def streams_bytes(self) -> int:
-        """Device bytes of the open stream-slot session (0: none)."""
+        """Device bytes of the open stream-slot session (0: none); the lo planes of FY_PRECISE count from the first precise call."""
         return int(_lib.lib().fy_flow_streams_bytes(self._h))
 
     def stream_slot_reset(self, slot: int):
@@ -182,7 +188,9 @@ class FlowEngine:
                           rand_noise: torch.Tensor, flags: int = 0) -> torch.Tensor:
         """One chunk pass for the streams in `slots`: row i of the inputs (shaped as `inference`'s) extends the stream of
         slots[i].  Always streaming=True, finalize=False.  -> mel (n, 80, 2*max(n_token)); row i is valid in
-        [:, :2*(n_token[i] - pre_lookahead)] and equals `inference(..., streaming=True, finalize=False)` on utterance i alone."""
+        [:, :2*(n_token[i] - pre_lookahead)] and equals `inference(..., streaming=True, finalize=False)` on utterance i alone.
+        flags: 0, or FY_PRECISE on a session opened with precise=True (equal to that call with the same flags; a slot continued in
+        the other arithmetic is recomputed in full); FY_DIRECT raises."""
         flags |= FY_STREAMING | FY_NO_FINALIZE
         n = len(slots)
         dev = self.device

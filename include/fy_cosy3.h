@@ -64,13 +64,15 @@ int fy_stream_destroy(void* stream);
 #define FY_PRECISE 1u /* split-bf16 (hi+lo) activations on the MFMA paths: fp32-class accuracy, 2x MFMA work */
 #define FY_DIRECT 2u  /* HiFT / DiT position conv: run convolutions on the exact fp32 VALU kernel */
 #define FY_STREAMING 4u /* flow: block-causal chunk attention mask (streaming=True in the reference) */
-#define FY_INCREMENTAL 16u /* flow, with FY_STREAMING | FY_NO_FINALIZE and B = 1: this call extends the previous FY_INCREMENTAL call of the
-                             handle (same prompt, the earlier tokens a prefix): only the new rows go through the DiT blocks, against the
-                             keys / values of the earlier rows kept per (Euler step, block).  Exact under the chunk mask when both calls end
-                             on a chunk boundary (the reference's schedule does).  After fy_flow_stream_reset, when the prompt lengths differ
-                             from the previous call's or the token count shrank, everything is computed and kept for the next call; a call
-                             whose length is not a whole number of chunks is computed whole and keeps NOTHING (the next call starts over).
-                             Same results as without the flag.
+#define FY_INCREMENTAL 16u /* flow, with FY_STREAMING | FY_NO_FINALIZE and B = 1, in the default arithmetic or with FY_PRECISE (not
+                             FY_DIRECT: such a call is computed whole and breaks the stream): this call extends the previous
+                             FY_INCREMENTAL call of the handle (same prompt, the earlier tokens a prefix, the same arithmetic - a call in
+                             the other one starts over and keeps its own rows): only the new rows go through the DiT blocks, against the
+                             keys / values of the earlier rows kept per (Euler step, block) - both bf16 planes of them under FY_PRECISE.
+                             Exact under the chunk mask when both calls end on a chunk boundary (the reference's schedule does).  After
+                             fy_flow_stream_reset, when the prompt lengths differ from the previous call's or the token count shrank,
+                             everything is computed and kept for the next call; a call whose length is not a whole number of chunks is
+                             computed whole and keeps NOTHING (the next call starts over). Same results as without the flag.
                              HiFT, B = 1, with or without FY_NO_FINALIZE (and with FY_DIRECT / FY_PRECISE): the call continues the handle's
                              stream.  It takes the whole mel so far (frames[0] = F) and the same wav layout, runs the vocoder over the
                              frames from a fixed margin before the samples already delivered (S_prev) only, and writes only wav[S_prev,
@@ -213,25 +215,34 @@ int fy_flow_stream_rows(const fy_flow* f);
  * pitch of cap_frames mel rows (prompt + generated) each, and the work buffers of the batched call; the single-stream state above
  * is separate and untouched.  Calls of a session are serial on one stream.
  * fy_flow_streams_open: allocates everything or nothing - at full size 2.7 MB per frame row and slot plus ~34 KB per row of work
- * buffers; FY_ERR_HIP with the bytes asked for when the device does not have them (no smaller fallback).  Opening again replaces
- * the session.  fy_flow_streams_close frees it; fy_flow_streams_bytes: the session's device bytes (0: none).
- * fy_flow_stream_slot_reset: the slot's next call starts a new stream.  fy_flow_stream_slot_rows: mel rows the slot has kept
- * (0: the next call computes everything; -1: no such slot).                                                                        */
+ * buffers (the lo planes of FY_PRECISE come with the first precise call, see fy_flow_infer_streams, and are counted from then on);
+ * FY_ERR_HIP with the bytes asked for when the device does not have them (no smaller fallback).  Opening again replaces the
+ * session.  fy_flow_streams_close frees it; fy_flow_streams_bytes: the session's device bytes (0: none).
+ * fy_flow_stream_slot_reset: the slot's next call starts a new stream.  fy_flow_stream_slot_rows: mel rows the slot has kept (0:
+ * the next call computes everything; -1: no such slot).                                                                            */
 int fy_flow_streams_open(fy_flow* f, int32_t n_slots, int32_t cap_frames);
 int fy_flow_streams_close(fy_flow* f);
 int64_t fy_flow_streams_bytes(const fy_flow* f);
+/* A session as opened takes the default arithmetic only (FY_PRECISE in fy_flow_infer_streams: FY_ERR_ARG, as before).  enable != 0:
+ * the session accepts FY_PRECISE calls from now on - nothing is allocated until the first one; 0: it refuses them again (lo planes
+ * that exist stay until close).  FY_ERR_STATE: no session.                                                                        */
+int fy_flow_streams_precise(fy_flow* f, int32_t enable);
 int fy_flow_stream_slot_reset(fy_flow* f, int32_t slot);
 int fy_flow_stream_slot_rows(const fy_flow* f, int32_t slot);
-/* Advance the streams in slots[0 .. n) (host int32, distinct) by one chunk each in ONE pass: utterance i of the inputs (packed
- * over the n utterances as fy_flow_infer's over B) extends the stream of slots[i]; mel out (n, 80, mel_frames), utterance i fills
- * frames [0, 2 * (n_token[i] - pre_lookahead)).  flags: FY_STREAMING | FY_NO_FINALIZE, default arithmetic.  Every slot follows
- * FY_INCREMENTAL's rules on its own: it extends when its previous call and this one end on a chunk boundary with the same prompt
- * lengths and no fewer tokens, otherwise its stream is computed in full (and kept, unless this call ends off a boundary).  Streams
- * may be at different chunk indices and lengths; a slot's first call brings all of its rows.  The new rows of all listed streams go
- * through every DiT product together, so the launch chain of a chunk pass is paid once per call; the results are bit for bit those
- * of fy_flow_infer(FY_STREAMING | FY_NO_FINALIZE) on each utterance alone.  FY_ERR_ARG (before any device work, the session as it
- * was): a slot out of range or listed twice, 2 * (tokens + prompt - look-ahead) above cap_frames, other flags; FY_ERR_STATE: no
- * session.  Lengths travel as kernel arguments: the call does not wait on the host.                                               */
+/* Advance the streams in slots[0 .. n) (host int32, distinct) by one chunk each in ONE pass: utterance i of the inputs (packed over
+ * the n utterances as fy_flow_infer's over B) extends the stream of slots[i]; mel out (n, 80, mel_frames), utterance i fills frames
+ * [0, 2 * (n_token[i] - pre_lookahead)).  flags: FY_STREAMING | FY_NO_FINALIZE, optionally FY_PRECISE (the fp32-class arithmetic,
+ * on a session enabled for it by fy_flow_streams_precise - FY_ERR_ARG otherwise; the session's first such call allocates the lo
+ * planes of its caches and work buffers - 2.7 MB more per frame row and slot - or fails with FY_ERR_HIP and the byte count, leaving
+ * the session usable in the default mode); FY_DIRECT is refused.  Each slot records the arithmetic its rows were kept in: a slot
+ * continued in the other one is recomputed in full (and kept), its neighbours are not.  Every slot follows FY_INCREMENTAL's rules
+ * on its own: it extends when its previous call and this one end on a chunk boundary with the same prompt lengths and no fewer
+ * tokens, otherwise its stream is computed in full (and kept, unless this call ends off a boundary).  Streams may be at different
+ * chunk indices and lengths; a slot's first call brings all of its rows.  The new rows of all listed streams go through every DiT
+ * product together, so the launch chain of a chunk pass is paid once per call; the results are bit for bit those of
+ * fy_flow_infer(FY_STREAMING | FY_NO_FINALIZE [| FY_PRECISE]) on each utterance alone.  FY_ERR_ARG (before any device work, the
+ * session as it was): a slot out of range or listed twice, 2 * (tokens + prompt - look-ahead) above cap_frames, other flags;
+ * FY_ERR_STATE: no session.  Lengths travel as kernel arguments: the call does not wait on the host.                               */
 int fy_flow_infer_streams(fy_flow* f, const int32_t* slots, int32_t n, const int32_t* token, int32_t tok_ld, const int32_t* n_token,
                           const int32_t* prompt_token, int32_t ptok_ld, const int32_t* n_prompt, const float* prompt_feat,
                           int32_t pfeat_rows, const int32_t* n_pfeat, const float* embedding, const float* rand_noise, int32_t noise_ld,
