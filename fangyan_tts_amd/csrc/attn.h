@@ -8,15 +8,20 @@
 int dit_attention(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin = 0,
                   bool interleaved = false);
 
-// the default kernel behind dit_attention (attn_dit.hip): row t of sequence s at row s * seq_rows + t * row_step
-int dit_attention2(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, int seq_rows, int row_step);
+// the default kernel behind dit_attention (attn_dit.hip): row t of sequence s at row s * seq_rows + t * row_step.  form: 0 = the
+// tiling rule chooses; 4 / 8 = that workgroup form whatever the length (the test hooks)
+int dit_attention2(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, int seq_rows, int row_step,
+                   int form = 0);
+// the round-2 kernel (attn.hip; dit_attention under FY_ATTN_V1=1, the cross-check) at W waves per workgroup: 4, or 8..16
+int dit_attention_v1(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, int seq_rows, int row_step,
+                     int W);
 
 // The per-sequence form of the same kernel (the flow decoder's stream slots): sequence s has its own first query row, length, base
 // row in qkv and first output row; frame t of it is row in_row + t * row_step of qkv, and query t >= q_begin is written to row
 // out_row + (t - q_begin) * row_step of out.  Tmax: the longest sequence (sizes the grid).  A query's result is what dit_attention
 // gives for the same row and keys.
 struct DitSeqTab { int q_begin, len, in_row, out_row; };
-int dit_attention_tab(const bf16_t* qkv, bf16_t* out, const DitSeqTab* tab, int nseq, int Tmax, int H, int chunk, int row_step, hipStream_t st);
+int dit_attention_tab(const bf16_t* qkv, bf16_t* out, const DitSeqTab* tab, int nseq, int Tmax, int H, int chunk, int row_step, hipStream_t st, int form = 0);
 
 // The split-operand form (fp32-class flow decoder): q, k, v and the output as x = hi + lo, two bf16 planes each, same layouts;
 // three MFMAs per product keep the hi x hi, hi x lo and lo x hi terms, softmax in fp32.

@@ -200,31 +200,27 @@ __global__ __launch_bounds__(AT_NW * 64) __attribute__((amdgpu_waves_per_eu(WPE,
 }
 
 
-int dit_attention(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, bool interleaved) {
-    FY_CHECK(qkv && out && seq_len && nseq >= 1 && Tmax >= 1 && H >= 1, FY_ERR_ARG, "dit_attention: bad arguments");
-    const float sl2 = 0.125f * 1.4426950408889634f;
+// Queries are cut into 32-row waves; the waves of a workgroup share the K/V tiles of their (sequence, head).  With 4-wave
+// workgroups (3 per CU) T = 400 gives 4 x H x nseq workgroups, a quarter of them with ONE live wave, and 1024 of them on 768
+// places take two rounds: 33.9 us per call at batch 8.  When a (sequence, head) fits one workgroup of <= 16 waves and those
+// workgroups cover at least half the CUs, one workgroup takes all of a pair's queries (4 waves per SIMD, Q fragments in LDS):
+// K/V are staged once per pair and the grid is a single round - 27.5 us (rocprofv3 over bench.py --no-pipeline).  From 8 waves
+// on the form needs no spill at 128 registers.
+static int dit_attention_v1_waves(int nseq, int Tmax, int H, int q_begin) {
     static int cus = 0;
     if (!cus) {
         int dev = 0;
         hipDeviceProp_t p;
         cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
     }
-    static const int force = getenv("FY_ATTN_WAVES") ? atoi(getenv("FY_ATTN_WAVES")) : 0;   // experiments and the equality test
-    // Queries are cut into 32-row waves; the waves of a workgroup share the K/V tiles of their (sequence, head).  With 4-wave
-    // workgroups (3 per CU) T = 400 gives 4 x H x nseq workgroups, a quarter of them with ONE live wave, and 1024 of them on 768
-    // places take two rounds: 33.9 us per call at batch 8.  When a (sequence, head) fits one workgroup of <= 16 waves and those
-    // workgroups cover at least half the CUs, one workgroup takes all of a pair's queries (4 waves per SIMD, Q fragments in LDS):
-    // K/V are staged once per pair and the grid is a single round - 27.5 us (rocprofv3 over bench.py --no-pipeline).  From 8 waves
-    // on the form needs no spill at 128 registers.
-    const int seq_rows = interleaved ? 1 : Tmax, row_step = interleaved ? nseq : 1;
-    static const int v1 = getenv("FY_ATTN_V1") ? atoi(getenv("FY_ATTN_V1")) : 0;            // the round-2 kernels (A/B measurements)
-    if (!v1) {
-        return dit_attention2(qkv, out, seq_len, nseq, Tmax, H, chunk, st, q_begin, seq_rows, row_step);
-    }
     const int nw = cdiv(Tmax, 32);
-    int W = 4;                                                   // waves per workgroup
-    if (force) W = force;
-    else if (nw >= 8 && nw <= 16 && H * nseq >= cus / 2 && q_begin == 0) W = nw;
+    return nw >= 8 && nw <= 16 && H * nseq >= cus / 2 && q_begin == 0 ? nw : 4;
+}
+
+int dit_attention_v1(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, int seq_rows, int row_step,
+                     int W) {
+    const float sl2 = 0.125f * 1.4426950408889634f;
+    const int nw = cdiv(Tmax, 32);
     if (W <= 4) {
         dim3 grid(cdiv(Tmax, 4 * 32), H, nseq);
         hipLaunchKernelGGL((dit_attention_k<4, 3>), grid, dim3(4 * 64), 0, st, qkv, out, seq_len, Tmax, H, chunk, sl2, q_begin, seq_rows, row_step);
@@ -241,6 +237,32 @@ int dit_attention(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, 
     }
     HIP_TRY(hipGetLastError());
     return FY_OK;
+}
+
+int dit_attention(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, bool interleaved) {
+    FY_CHECK(qkv && out && seq_len && nseq >= 1 && Tmax >= 1 && H >= 1, FY_ERR_ARG, "dit_attention: bad arguments");
+    static const int force = getenv("FY_ATTN_WAVES") ? atoi(getenv("FY_ATTN_WAVES")) : 0;   // experiments and the equality test
+    const int seq_rows = interleaved ? 1 : Tmax, row_step = interleaved ? nseq : 1;
+    static const int v1 = getenv("FY_ATTN_V1") ? atoi(getenv("FY_ATTN_V1")) : 0;            // the round-2 kernels (A/B measurements)
+    if (!v1) {
+        return dit_attention2(qkv, out, seq_len, nseq, Tmax, H, chunk, st, q_begin, seq_rows, row_step);
+    }
+    return dit_attention_v1(qkv, out, seq_len, nseq, Tmax, H, chunk, st, q_begin, seq_rows, row_step, force ? force : dit_attention_v1_waves(nseq, Tmax, H, q_begin));
+}
+
+// test hook (tests/test_attention_gpu.py): dit_attention with the kernel and its workgroup form chosen by the caller, not by the
+// environment.  kernel 0: the round-5 kernel (attn_dit.hip), waves 4 / 8; kernel 1: the round-2 kernel above, waves 4 or 8..16;
+// waves 0: the kernel's own rule
+extern "C" int fy_debug_dit_attention(const void* qkv, void* out, const int32_t* seq_len, int32_t nseq, int32_t Tmax, int32_t H, int32_t chunk, int32_t q_begin,
+                                      int32_t interleaved, int32_t kernel, int32_t waves, void* stream) {
+    FY_CHECK(qkv && out && seq_len && nseq >= 1 && Tmax >= 1 && H >= 1 && chunk >= 0 && q_begin >= 0, FY_ERR_ARG, "fy_debug_dit_attention: bad arguments");
+    FY_CHECK(kernel == 0 ? (waves == 0 || waves == 4 || waves == 8) : kernel == 1 && (waves == 0 || waves == 4 || (waves >= 8 && waves <= 16)), FY_ERR_ARG,
+             "fy_debug_dit_attention: kernel %d has no %d-wave form", kernel, waves);
+    const int seq_rows = interleaved ? 1 : Tmax, row_step = interleaved ? nseq : 1;
+    hipStream_t st = (hipStream_t)stream;
+    if (kernel == 0) return dit_attention2((const bf16_t*)qkv, (bf16_t*)out, seq_len, nseq, Tmax, H, chunk, st, q_begin, seq_rows, row_step, waves);
+    return dit_attention_v1((const bf16_t*)qkv, (bf16_t*)out, seq_len, nseq, Tmax, H, chunk, st, q_begin, seq_rows, row_step,
+                            waves ? waves : dit_attention_v1_waves(nseq, Tmax, H, q_begin));
 }
 
 // -----------------------------------------------------------------------------------------------
@@ -475,6 +497,19 @@ int dit_attention_split_tab(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* 
                             int row_step, hipStream_t st) {
     FY_CHECK(qkv_hi && qkv_lo && out_hi && out_lo && tab && nseq >= 1 && Tmax >= 1 && H >= 1 && row_step >= 1, FY_ERR_ARG, "dit_attention_split_tab: bad arguments");
     return dit_attention_split_any<true>(qkv_hi, qkv_lo, out_hi, out_lo, reinterpret_cast<const int*>(tab), nseq, Tmax, H, chunk, row_step, st);
+}
+
+// test hooks (tests/test_attention_gpu.py): the split-operand forms as the flow decoder calls them
+extern "C" int fy_debug_dit_attention_split(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, const int32_t* seq_len, int32_t nseq, int32_t Tmax,
+                                            int32_t H, int32_t chunk, void* stream) {
+    FY_CHECK(chunk >= 0, FY_ERR_ARG, "fy_debug_dit_attention_split: bad arguments");
+    return dit_attention_split((const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo, (bf16_t*)out_hi, (bf16_t*)out_lo, seq_len, nseq, Tmax, H, chunk, (hipStream_t)stream);
+}
+extern "C" int fy_debug_dit_attention_split_tab(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, const void* tab, int32_t nseq, int32_t Tmax,
+                                                int32_t H, int32_t chunk, int32_t row_step, void* stream) {
+    FY_CHECK(chunk >= 0, FY_ERR_ARG, "fy_debug_dit_attention_split_tab: bad arguments");
+    return dit_attention_split_tab((const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo, (bf16_t*)out_hi, (bf16_t*)out_lo, (const DitSeqTab*)tab, nseq, Tmax, H, chunk, row_step,
+                                   (hipStream_t)stream);
 }
 
 // -----------------------------------------------------------------------------------------------

@@ -361,17 +361,25 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 #undef SB
 
-int dit_attention2(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, int seq_rows, int row_step) {
+// the tiling rule: 64 queries per wave.  Up to 256 frames: four waves per workgroup; longer sequences: eight (512 queries, one
+// workgroup per CU) - at the benchmark's 400 frames a (sequence, head)'s keys and values are then fetched once, not once per 256
+// queries (52 MB instead of 78 per call: at 16 x 400 x 16 heads the call moves as long as it computes)
+// Which: the tiling whose last workgroup of a sequence is fuller (650 frames = 21 blocks: 2 x 16 slots of the eight-wave form
+// leave every second CU idle two thirds of the launch; 3 x 8 slots do not), the eight-wave form on a tie.
+// form: 4 / 8 force that workgroup form (the test hooks); 0 everywhere else
+static bool at2_four_waves(int Tmax, int form) {
+    if (form) return form == 4;
+    const int nqb = cdiv(Tmax, 32), g8 = cdiv(nqb, 16), g4 = cdiv(nqb, 8);
+    return Tmax <= 256 || 10 * nqb * (2 * g8 - g4) > g4 * g8 * 16;                   // nqb / (8 g4) > nqb / (16 g8) + 0.1
+}
+
+int dit_attention2(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq, int Tmax, int H, int chunk, hipStream_t st, int q_begin, int seq_rows, int row_step,
+                   int form) {
+    FY_CHECK(form == 0 || form == 4 || form == 8, FY_ERR_ARG, "dit_attention2: no %d-wave form", form);
     const float sl2 = 0.125f * 1.4426950408889634f;
     ProfScope prof("dit_attention", 0.0, st);
-    // 64 queries per wave.  Up to 256 frames: four waves per workgroup; longer sequences: eight (512 queries, one workgroup per CU) -
-    // at the benchmark's 400 frames a (sequence, head)'s keys and values are then fetched once, not once per 256 queries
-    // (52 MB instead of 78 per call: at 16 x 400 x 16 heads the call moves as long as it computes)
-    // Which: the tiling whose last workgroup of a sequence is fuller (650 frames = 21 blocks: 2 x 16 slots of the eight-wave form
-    // leave every second CU idle two thirds of the launch; 3 x 8 slots do not), the eight-wave form on a tie.
     const int nqb = cdiv(Tmax, 32), g8 = cdiv(nqb, 16), g4 = cdiv(nqb, 8);
-    const bool four = Tmax <= 256 || 10 * nqb * (2 * g8 - g4) > g4 * g8 * 16;        // nqb / (8 g4) > nqb / (16 g8) + 0.1
-    if (four) {
+    if (at2_four_waves(Tmax, form)) {
         dim3 grid(g4, H, nseq);
         hipLaunchKernelGGL((dit_attention2_k<4, true>), grid, dim3(256), 0, st, qkv, out, seq_len, Tmax, H, chunk, sl2, q_begin, seq_rows, row_step);
     } else {
@@ -382,16 +390,23 @@ int dit_attention2(const bf16_t* qkv, bf16_t* out, const int* seq_len, int nseq,
     return FY_OK;
 }
 
-int dit_attention_tab(const bf16_t* qkv, bf16_t* out, const DitSeqTab* tab, int nseq, int Tmax, int H, int chunk, int row_step, hipStream_t st) {
+int dit_attention_tab(const bf16_t* qkv, bf16_t* out, const DitSeqTab* tab, int nseq, int Tmax, int H, int chunk, int row_step, hipStream_t st, int form) {
     FY_CHECK(qkv && out && tab && nseq >= 1 && Tmax >= 1 && H >= 1 && row_step >= 1, FY_ERR_ARG, "dit_attention_tab: bad arguments");
+    FY_CHECK(form == 0 || form == 4 || form == 8, FY_ERR_ARG, "dit_attention_tab: no %d-wave form", form);
     const float sl2 = 0.125f * 1.4426950408889634f;
     ProfScope prof("dit_attention", 0.0, st);
     // the tiling rule of dit_attention2, on the longest sequence
     const int nqb = cdiv(Tmax, 32), g8 = cdiv(nqb, 16), g4 = cdiv(nqb, 8);
-    const bool four = Tmax <= 256 || 10 * nqb * (2 * g8 - g4) > g4 * g8 * 16;
     const int* t = reinterpret_cast<const int*>(tab);
-    if (four) hipLaunchKernelGGL((dit_attention2_k<4, true, true>), dim3(g4, H, nseq), dim3(256), 0, st, qkv, out, t, Tmax, H, chunk, sl2, 0, 0, row_step);
+    if (at2_four_waves(Tmax, form)) hipLaunchKernelGGL((dit_attention2_k<4, true, true>), dim3(g4, H, nseq), dim3(256), 0, st, qkv, out, t, Tmax, H, chunk, sl2, 0, 0, row_step);
     else hipLaunchKernelGGL((dit_attention2_k<8, true, true>), dim3(g8, H, nseq), dim3(512), 0, st, qkv, out, t, Tmax, H, chunk, sl2, 0, 0, row_step);
     HIP_TRY(hipGetLastError());
     return FY_OK;
+}
+
+// test hook (tests/test_attention_gpu.py): dit_attention_tab with the workgroup form forced (waves = 4 / 8; 0 = the tiling rule)
+extern "C" int fy_debug_dit_attention_tab(const void* qkv, void* out, const void* tab, int32_t nseq, int32_t Tmax, int32_t H, int32_t chunk, int32_t row_step,
+                                          int32_t waves, void* stream) {
+    FY_CHECK(chunk >= 0, FY_ERR_ARG, "fy_debug_dit_attention_tab: bad arguments");
+    return dit_attention_tab((const bf16_t*)qkv, (bf16_t*)out, (const DitSeqTab*)tab, nseq, Tmax, H, chunk, row_step, (hipStream_t)stream, waves);
 }
