@@ -44,6 +44,7 @@ FY_DIRECT = 2
 FY_STREAMING = 4
 FY_NO_FINALIZE = 8
 FY_INCREMENTAL = 16
+FY_PACKED = 32
 FY_LLM_KEEP_LOGP = 4
 
 _lib = None
@@ -105,6 +106,8 @@ def _declare(L):
     L.fy_flow_destroy.argtypes = [vp]
     L.fy_flow_destroy.restype = None
     L.fy_flow_infer.argtypes = [vp, vp, i32, i32p, vp, i32, i32p, f32p, i32, i32p, f32p, f32p, i32, i32, f32p, i32, u32, vp]
+    L.fy_flow_last_rows.argtypes = [vp]
+    L.fy_flow_last_rows.restype = C.c_int64
     L.fy_flow_stream_reset.argtypes = [vp]
     L.fy_flow_stream_rows.argtypes = [vp]
     L.fy_flow_streams_open.argtypes = [vp, i32, i32]
@@ -158,6 +161,7 @@ def _declare(L):
     L.fy_llm_weight_planes.argtypes = [vp]
     L.fy_set_host_wait.argtypes = [i32, i32]
     L.fy_flow_weight_planes.argtypes = [vp]
+    L.fy_flow_ln_fold.argtypes = [vp]
     L.fy_debug_decode_stamps.argtypes = [vp, C.POINTER(C.c_uint64), i32, vp]
     L.fy_debug_decode32_stamps.argtypes = [vp, C.POINTER(C.c_uint64), i32, vp]
     L.fy_debug_gemm_exact.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp]

@@ -161,6 +161,9 @@ class CosyVoice3Model:
         # precision modes of the two back stages (include/fy_cosy3.h): 0 = bf16 MFMA operands (default); FY_PRECISE = fp32-class
         # (split operands, fp32 attention); for the vocoder also FY_DIRECT = exact fp32 convolutions.  Verification modes.
         self.flow_flags, self.hift_flags = 0, 0
+        # True: ragged flow batches (tts_batch, tts_pipeline's flow workers, voice conversion, the final-pass groups of
+        # tts_stream_batch) send only their valid rows through the DiT blocks (FY_PACKED): the same mel, bit for bit
+        self.flow_packed = False
         self.lock = threading.Lock()          # the engines' handles are single-threaded
         # "greedy": the deterministic rule of SURVEY 8 a4.  "ras": the reference's default repetition-aware sampling; its
         # multinomial draws come from fresh uniforms (one row per sequence slot) drawn before every LM call
@@ -643,7 +646,7 @@ class CosyVoice3Model:
         ln = ln or self.lanes[0]
         B = len(inputs)
         ptok, n_fp, pfeat, n_pf, emb = self._prompt_tensors(inputs)
-        mel = ln.flow.inference(out, n_tok, ptok, n_fp, pfeat, n_pf, emb, self.rand_noise, flags=self.flow_flags)
+        mel = ln.flow.inference(out, n_tok, ptok, n_fp, pfeat, n_pf, emb, self.rand_noise, flags=self.flow_flags, packed=self.flow_packed)
         frames = [2 * n for n in n_tok]
         if speed != 1.0:                                    # cli/model.py:435-437
             assert B == 1, "speed change only supports a single utterance"
@@ -811,7 +814,8 @@ class CosyVoice3Model:
                             raise RuntimeError("the language model emitted no speech token for an utterance")
                         ix = torch.tensor(grp, device=self.device)
                         mel = ln.flow.inference(out[ix, : max(n[i] for i in grp)].contiguous(), [n[i] for i in grp], ptok[ix], [n_fp[i] for i in grp],
-                                                pfeat[ix], [n_pf[i] for i in grp], emb[ix], self.rand_noise, flags=self.flow_flags)
+                                                pfeat[ix], [n_pf[i] for i in grp], emb[ix], self.rand_noise, flags=self.flow_flags,
+                                                packed=self.flow_packed)
                         for j, i in enumerate(grp):
                             grow(i, mel[j: j + 1], n[i], True)
                             ln.llm.release(i)

@@ -66,6 +66,13 @@ struct fy_flow {
     int inc_mode = 0;                                   // the arithmetic the kept rows were computed in (0 default, 1 FY_PRECISE): a call in the other one starts over
     int inc_np = -1, inc_npf = -1, inc_ntok = -1;       // the stream's prompt tokens / prompt frames / tokens at the last kept call (a cheap check that a call extends it)
     struct FlowStreams* ss = nullptr;                   // the stream-slot session (fy_flow_streams_open), or none
+    // packed rows (FY_PACKED): the tables of a ragged call whose blocks run on the valid rows only, sized for 2 max_batch Tmax rows
+    // on the first packed call - per compact row (front row, compact row, frame, sequence) and the rotary table row of its frame
+    // (the qkv product's epilogue looks its table up by row index), and the DitSeqTab of the 2 max_batch sequences
+    int4* pk_rows = nullptr;
+    float2* pk_rope = nullptr;
+    int* pk_tab = nullptr;
+    int64_t last_rows = 0;                              // rows the last fy_flow_infer call pushed through each block's products
     ~fy_flow();
 };
 
@@ -354,6 +361,35 @@ __global__ void stream_euler_k(const float* __restrict__ xs, float* __restrict__
     const int4 rw = rows[2 * fr];
     const long o = ((long)rw.w * cap + rw.z) * C + c;
     xs_next[o] = euler_update(xs[o], v[(2L * fr) * C + c], v[(2L * fr + 1) * C + c], dt, cfg);
+}
+
+// ---- packed rows (FY_PACKED): the blocks of fy_flow_infer on the valid rows of a ragged batch ----------------------------------
+// Sequence s = 2 b + sq sits at the compact rows [tab[s].in_row, + tab[s].len), frame after frame, the sequences back to back in
+// the order of s (flow.py: packed_rows).  Per compact row: its row in the padded front layout, itself, its frame and its sequence
+// (stream_gather_k reads .x), and a copy of the rotary table's row of its frame - the qkv product's epilogue finds a row's position
+// from its index, so a table with one row per compact row keeps the rotation there.  16 lanes per row, 16 bytes each.
+__global__ __launch_bounds__(256) void packed_tables_k(const int* __restrict__ tab, int nseq, int Tp, const float2* __restrict__ rope, int rope_half,
+                                                       int4* __restrict__ rows, float2* __restrict__ prope, int Mp) {
+    const int r = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
+    if (r >= Mp) return;
+    int s = 0;
+    while (s + 1 < nseq && tab[4 * (s + 1) + 2] <= r) ++s;
+    const int t = r - tab[4 * s + 2];
+    if (l == 0) rows[r] = make_int4(s * Tp + t, r, t, s);
+    const float4* src = reinterpret_cast<const float4*>(rope + (long)t * rope_half);
+    float4* dst = reinterpret_cast<float4*>(prope + (long)r * rope_half);
+    for (int k = l; k < rope_half / 2; k += 16) dst[k] = src[k];
+}
+// euler_k with v at the compact rows of the utterance's two sequences; x stays in the padded layout the next step's front reads.
+// One element per lane like euler_k, not four: with the four updates of a 16-byte access side by side the compiler contracts
+// euler_update's (1 + cfg) vc - cfg vu into a packed multiply-add, where euler_k rounds both products - one rounding apart, and
+// the packed call must give the padded call's bits.  A wave still reads and writes whole contiguous rows.
+__global__ void packed_euler_k(float* __restrict__ x, const float* __restrict__ v, const int* __restrict__ tab, int Tmax, int C, float dt, float cfg) {
+    const int b = blockIdx.y, t = blockIdx.x, c = threadIdx.x;
+    if (t >= tab[8 * b + 1] || c >= C) return;
+    const float vc = v[((long)tab[8 * b + 2] + t) * C + c], vu = v[((long)tab[8 * b + 6] + t) * C + c];
+    const long o = ((long)b * Tmax + t) * C + c;
+    x[o] = euler_update(x[o], vc, vu, dt, cfg);
 }
 
 __global__ void silu_k(const float* __restrict__ a, float* __restrict__ o, long n) {
@@ -681,6 +717,7 @@ extern "C" int fy_flow_create(fy_flow** out, const fy_flow_config* cfg, const fy
 extern "C" void fy_flow_destroy(fy_flow* f) { delete f; }
 
 extern "C" int fy_flow_weight_planes(const fy_flow* f) { return f ? f->planes : 0; }
+extern "C" int fy_flow_ln_fold(const fy_flow* f) { return f ? (f->fold ? 1 : 0) : -1; }
 
 // lo planes of the fp32-class mode, sized for the handle's capacity, on first use
 static int ensure_precise(fy_flow* f) {
@@ -697,7 +734,13 @@ static int ensure_precise(fy_flow* f) {
 
 // ---- estimator ----------------------------------------------------------------------------------------
 // One DiT.forward over nseq sequences whose bf16 input rows are in f->a_in; result rows (fp32, C wide) in f->v.
-static int dit_forward(fy_flow* f, int nseq, int Tmax, int slot, bool streaming, uint32_t flags, hipStream_t st) {
+// pk (FY_PACKED, fy_flow_infer): the input projection and the position convolutions run in that layout as always; then the valid rows
+// are gathered into one compact run (c1, free once the second convolution has read it) and ONLY those pk->Mp rows go through the
+// blocks, the final LayerNorm-modulate and the output projection: the same products, LayerNorm fold included, on fewer rows - a
+// row's sums depend neither on M nor on the rows beside it - the per-sequence form of the same attention kernel at the same Tmax,
+// and the rotary epilogue on a table with one row per compact row.  The result rows in f->v are compact as well.
+struct FlowPacked { int Mp; const int4* rows; const DitSeqTab* tab; const float2* rope; };
+static int dit_forward(fy_flow* f, int nseq, int Tmax, int slot, bool streaming, uint32_t flags, hipStream_t st, const FlowPacked* pk = nullptr) {
     const fy_flow_config& c = f->cfg;
     const int D = c.dim, C = c.mel, inner = c.heads * c.head_dim, FF = D * c.ff_mult;
     const int M = nseq * Tmax;
@@ -725,6 +768,12 @@ static int dit_forward(fy_flow* f, int nseq, int Tmax, int slot, bool streaming,
         d.add_resid = 1; d.resid = f->h; d.r_bs = (long)Tmax * D; d.r_ld = D;
         FY_TRY(mf ? conv1d_bf16_mfma(d, f->pos2, (flags & FY_PRECISE) != 0, st) : conv1d_f32_direct(d, f->pos2, st));
     }
+    float* h = f->h;                                     // the residual stream of the blocks, Mb rows
+    int Mb = M;
+    if (pk) {
+        h = f->c1; Mb = pk->Mp;
+        hipLaunchKernelGGL(stream_gather_k, dim3(Mb), dim3(256), 0, st, f->h, pk->rows, h, D);
+    }
     const float* modbase = f->mod + (size_t)slot * c.depth * 6 * D;
     bf16_t* const xn_lo = pr ? f->xn_lo : nullptr;
     // LayerNorm-modulate folded across the qkv / ff1 products (round 5).  xn = LN(h) (1 + s) + b feeds ONE product each time, and s, b
@@ -748,52 +797,54 @@ static int dit_forward(fy_flow* f, int nseq, int Tmax, int slot, bool streaming,
         const FlowBlockW& k = f->blk[i];
         const float* m = modbase + (size_t)i * 6 * D;       // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
         const bool fold_q = fold && i > 0;                  // block 0's h comes from the position convolution
-        if (!fold_q) hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(M, 4)), dim3(256), 0, st, f->h, m + D, m, f->xn, xn_lo, M, D);
+        if (!fold_q) hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mb, 4)), dim3(256), 0, st, h, m + D, m, f->xn, xn_lo, Mb, D);
         GemmEpi q;
         q.bias = k.bqkv; q.out = f->qkv; q.out_bf16 = 1; q.ldc = 3 * inner;
         // x-transformers rotary embedding (head 0 of q and k only, modules.py:368-373) in the projection's epilogue, on the fp32
         // sums before they are rounded to bf16 (or split into the two planes)
-        q.rope = f->rope; q.rope_T = Tmax; q.rope_half = c.head_dim / 2; q.rope_stride = inner;
+        q.rope = pk ? pk->rope : f->rope; q.rope_T = pk ? Mb : Tmax; q.rope_half = c.head_dim / 2; q.rope_stride = inner;
         if (pr) {
             q.a_lo = f->xn_lo; q.out_lo = f->qkv_lo; q.w_lo = k.wqkv_lo;
-            FY_TRY(gemm_split(f->xn, D, k.wqkv, M, 3 * inner, D, q, st));
-            FY_TRY(dit_attention_split(f->qkv, f->qkv_lo, f->ao, f->ao_lo, f->seq_len, nseq, Tmax, c.heads, streaming ? c.static_chunk : 0, st));
+            FY_TRY(gemm_split(f->xn, D, k.wqkv, Mb, 3 * inner, D, q, st));
+            if (pk) FY_TRY(dit_attention_split_tab(f->qkv, f->qkv_lo, f->ao, f->ao_lo, pk->tab, nseq, Tmax, c.heads, streaming ? c.static_chunk : 0, 1, st));
+            else FY_TRY(dit_attention_split(f->qkv, f->qkv_lo, f->ao, f->ao_lo, f->seq_len, nseq, Tmax, c.heads, streaming ? c.static_chunk : 0, st));
         } else {
             if (fold_q) {
                 const size_t sb = sb0 + i, QN = (size_t)3 * inner;
                 q.bias = f->bq_fold + sb * QN; q.ln_rows_slots = f->ln_slots; q.ln_dim = D; q.ln_u = f->uq_fold + sb * QN;
-                FY_TRY(gemm_bf16(f->hb, D, f->wq_fold + sb * QN * D, M, 3 * inner, D, q, st));
-            } else FY_TRY(gemm_bf16(f->xn, D, k.wqkv, M, 3 * inner, D, q, st));
-            FY_TRY(dit_attention(f->qkv, f->ao, f->seq_len, nseq, Tmax, c.heads, streaming ? c.static_chunk : 0, st));
+                FY_TRY(gemm_bf16(f->hb, D, f->wq_fold + sb * QN * D, Mb, 3 * inner, D, q, st));
+            } else FY_TRY(gemm_bf16(f->xn, D, k.wqkv, Mb, 3 * inner, D, q, st));
+            if (pk) FY_TRY(dit_attention_tab(f->qkv, f->ao, pk->tab, nseq, Tmax, c.heads, streaming ? c.static_chunk : 0, 1, st));
+            else FY_TRY(dit_attention(f->qkv, f->ao, f->seq_len, nseq, Tmax, c.heads, streaming ? c.static_chunk : 0, st));
         }
         GemmEpi o;
-        o.mode = EPI_GATE_RESID; o.bias = k.bo; o.resid = f->h; o.gate = m + 2 * D; o.ldc = D;
+        o.mode = EPI_GATE_RESID; o.bias = k.bo; o.resid = h; o.gate = m + 2 * D; o.ldc = D;
         if (fold) producer(o);
-        if (pr) { o.a_lo = f->ao_lo; o.w_lo = k.wo_lo; o.gate_ones = f->ones; FY_TRY(gemm_split(f->ao, inner, k.wo, M, D, inner, o, st)); }
-        else FY_TRY(gemm_bf16(f->ao, inner, k.wo, M, D, inner, o, st));
+        if (pr) { o.a_lo = f->ao_lo; o.w_lo = k.wo_lo; o.gate_ones = f->ones; FY_TRY(gemm_split(f->ao, inner, k.wo, Mb, D, inner, o, st)); }
+        else FY_TRY(gemm_bf16(f->ao, inner, k.wo, Mb, D, inner, o, st));
         GemmEpi g;
         g.bias = k.b1; g.act = ACT_GELU_TANH; g.out = f->ff; g.out_bf16 = 1; g.ldc = FF;
         if (fold) {
             const size_t sb = sb0 + i;
             g.bias = f->b1_fold + sb * FF; g.ln_rows_slots = f->ln_slots; g.ln_dim = D; g.ln_u = f->u1_fold + sb * FF;
-            FY_TRY(gemm_bf16(f->hb, D, f->w1_fold + sb * (size_t)FF * D, M, FF, D, g, st));
+            FY_TRY(gemm_bf16(f->hb, D, f->w1_fold + sb * (size_t)FF * D, Mb, FF, D, g, st));
         } else {
-            hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(M, 4)), dim3(256), 0, st, f->h, m + 4 * D, m + 3 * D, f->xn, xn_lo, M, D);
-            if (pr) { g.a_lo = f->xn_lo; g.out_lo = f->ff_lo; g.w_lo = k.w1_lo; FY_TRY(gemm_split(f->xn, D, k.w1, M, FF, D, g, st)); }
-            else FY_TRY(gemm_bf16(f->xn, D, k.w1, M, FF, D, g, st));
+            hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mb, 4)), dim3(256), 0, st, h, m + 4 * D, m + 3 * D, f->xn, xn_lo, Mb, D);
+            if (pr) { g.a_lo = f->xn_lo; g.out_lo = f->ff_lo; g.w_lo = k.w1_lo; FY_TRY(gemm_split(f->xn, D, k.w1, Mb, FF, D, g, st)); }
+            else FY_TRY(gemm_bf16(f->xn, D, k.w1, Mb, FF, D, g, st));
         }
         GemmEpi r;
-        r.mode = EPI_GATE_RESID; r.bias = k.b2; r.resid = f->h; r.gate = m + 5 * D; r.ldc = D;
+        r.mode = EPI_GATE_RESID; r.bias = k.b2; r.resid = h; r.gate = m + 5 * D; r.ldc = D;
         if (fold && i + 1 < c.depth) producer(r);
-        if (pr) { r.a_lo = f->ff_lo; r.w_lo = k.w2_lo; r.gate_ones = f->ones; FY_TRY(gemm_split(f->ff, FF, k.w2, M, D, FF, r, st)); }
-        else FY_TRY(gemm_bf16(f->ff, FF, k.w2, M, D, FF, r, st));
+        if (pr) { r.a_lo = f->ff_lo; r.w_lo = k.w2_lo; r.gate_ones = f->ones; FY_TRY(gemm_split(f->ff, FF, k.w2, Mb, D, FF, r, st)); }
+        else FY_TRY(gemm_bf16(f->ff, FF, k.w2, Mb, D, FF, r, st));
     }
     const float* fn = f->fin + (size_t)slot * 2 * D;            // (scale, shift), modules.py:261
-    hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(M, 4)), dim3(256), 0, st, f->h, fn, fn + D, f->xn, xn_lo, M, D);
+    hipLaunchKernelGGL(ln_mod_k, dim3(cdiv(Mb, 4)), dim3(256), 0, st, h, fn, fn + D, f->xn, xn_lo, Mb, D);
     GemmEpi p;
     p.bias = f->b_out; p.out = f->v; p.out_bf16 = 0; p.ldc = C;
-    if (pr) { p.a_lo = f->xn_lo; p.w_lo = f->w_out_lo; p.gate_ones = f->ones; FY_TRY(gemm_split(f->xn, D, f->w_out, M, C, D, p, st)); }
-    else FY_TRY(gemm_bf16(f->xn, D, f->w_out, M, C, D, p, st));
+    if (pr) { p.a_lo = f->xn_lo; p.w_lo = f->w_out_lo; p.gate_ones = f->ones; FY_TRY(gemm_split(f->xn, D, f->w_out, Mb, C, D, p, st)); }
+    else FY_TRY(gemm_bf16(f->xn, D, f->w_out, Mb, C, D, p, st));
     HIP_TRY(hipGetLastError());
     return FY_OK;
 }
@@ -933,6 +984,29 @@ static int flow_front(fy_flow* f, const FlowFront& w, const int32_t* token, int 
     return conv1d_f32_mfma(e, f->pre2, st);
 }
 
+// the tables of FY_PACKED, sized for the handle's capacity, on the first packed call: all three or none
+static int ensure_packed(fy_flow* f) {
+    if (f->pk_rows) return FY_OK;
+    const size_t R = (size_t)2 * f->max_batch * f->Tmax, half = f->cfg.head_dim / 2;
+    const size_t counts[3] = {R * sizeof(int4), R * half * sizeof(float2), (size_t)2 * f->max_batch * sizeof(DitSeqTab)};
+    const size_t need = counts[0] + counts[1] + counts[2];
+    void* got[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; ++i) {
+        hipError_t e = hipMalloc(&got[i], counts[i] + 256);
+        if (e != hipSuccess) {
+            for (int j = 0; j < i; ++j) (void)hipFree(got[j]);
+            fy_set_error("fy_flow_infer: hipMalloc(%zu B) of the %zu bytes of row tables (FY_PACKED) failed: %s", counts[i], need, hipGetErrorString(e));
+            return FY_ERR_HIP;
+        }
+    }
+    for (int i = 0; i < 3; ++i) f->pool.ptrs.push_back(got[i]);
+    f->pool.bytes += need;
+    f->pk_rows = (int4*)got[0]; f->pk_rope = (float2*)got[1]; f->pk_tab = (int*)got[2];
+    return FY_OK;
+}
+
+extern "C" int64_t fy_flow_last_rows(const fy_flow* f) { return f ? f->last_rows : -1; }
+
 extern "C" int fy_flow_infer(fy_flow* f, const int32_t* token, int32_t tok_ld, const int32_t* n_token, const int32_t* prompt_token,
                              int32_t ptok_ld, const int32_t* n_prompt, const float* prompt_feat, int32_t pfeat_rows, const int32_t* n_pfeat,
                              const float* embedding, const float* rand_noise, int32_t noise_ld, int32_t B, float* mel, int32_t mel_frames,
@@ -957,6 +1031,25 @@ extern "C" int fy_flow_infer(fy_flow* f, const int32_t* token, int32_t tok_ld, c
         sl[2 * b] = sl[2 * b + 1] = T;
         Tmax = std::max(Tmax, T); Nmax = std::max(Nmax, n_all);
     }
+    // FY_PACKED: the blocks on the valid rows only (dit_forward says how).  A call whose lengths are all equal (B = 1 among them, so
+    // every FY_INCREMENTAL call that extends a stream) has no other rows and takes the padded path; so does a process that runs the
+    // round-2 attention kernels (FY_ATTN_V1, A/B measurements), which have no per-sequence form.  Sequence 2 b + sq starts where
+    // sequence 2 b + sq - 1 ends.
+    std::vector<int> ptab(8 * mb, 0);
+    int Mp = 0;
+    bool ragged = false;
+    for (int b = 0; b < B; ++b) {
+        const int T = lens[1 * mb + b];
+        ragged = ragged || T != Tmax;
+        for (int sq = 0; sq < 2; ++sq) {
+            int* a = ptab.data() + 4 * (2 * b + sq);
+            a[0] = 0; a[1] = T; a[2] = a[3] = Mp;
+            Mp += T;
+        }
+    }
+    static const bool attn_v1 = getenv("FY_ATTN_V1") && atoi(getenv("FY_ATTN_V1")) != 0;
+    const bool packed = (flags & FY_PACKED) && ragged && !attn_v1;
+    if (packed) FY_TRY(ensure_packed(f));                 // (nothing launched yet)
     // by kernel argument, not by copy + synchronisation: the call can be enqueued behind a previous one that is still running
     FY_TRY(upload_ints(f->blen, lens.data(), (int)lens.size(), st));
     FY_TRY(upload_ints(f->seq_len, sl.data(), (int)sl.size(), st));
@@ -994,17 +1087,25 @@ extern "C" int fy_flow_infer(fy_flow* f, const int32_t* token, int32_t tok_ld, c
         }
         HIP_TRY(hipMemcpyAsync(xs + c.n_timesteps * xslice + (size_t)T0 * C, f->x + (size_t)T0 * C, (size_t)(Tmax - T0) * C * sizeof(float), hipMemcpyDeviceToDevice, st));
         f->inc_T = Tmax;
+        f->last_rows = 2 * (int64_t)(Tmax - T0);
         const int F = 2 * (n_token[0] + n_prompt[0] - look) - n_pfeat[0];
         FY_TRY(transpose_blc_to_bcl(xs + c.n_timesteps * xslice + (size_t)n_pfeat[0] * C, mel, 1, C, F, 0, C, 0, mel_frames, st));
         HIP_TRY(hipGetLastError());
         return FY_OK;
     }
     if (flags & FY_INCREMENTAL) f->inc_T = 0;             // a call that could not be incremental breaks the stream
+    FlowPacked pk{Mp, f->pk_rows, reinterpret_cast<const DitSeqTab*>(f->pk_tab), f->pk_rope};
+    if (packed) {
+        FY_TRY(upload_ints(f->pk_tab, ptab.data(), 8 * B, st));
+        hipLaunchKernelGGL(packed_tables_k, dim3(cdiv(Mp, 16)), dim3(256), 0, st, f->pk_tab, 2 * B, Tmax, f->rope, c.head_dim / 2, f->pk_rows, f->pk_rope, Mp);
+    }
+    f->last_rows = packed ? (int64_t)Mp : 2 * (int64_t)B * Tmax;
     for (int step = 0; step < c.n_timesteps; ++step) {
         hipLaunchKernelGGL(dit_assemble_k, dim3(Tmax, 2 * B), dim3(4 * C), 0, st, f->x, f->cond, f->mu, f->spks, d_T, f->a_in,
                            (flags & FY_PRECISE) ? f->a_in_lo : nullptr, Tmax, C, Tmax, 1);
-        FY_TRY(dit_forward(f, 2 * B, Tmax, step, (flags & FY_STREAMING) != 0, flags, st));
-        hipLaunchKernelGGL(euler_k, dim3(Tmax, B), dim3(128), 0, st, f->x, f->v, d_T, Tmax, C, f->dt_of_step[step], c.cfg_rate, 0, 0);
+        FY_TRY(dit_forward(f, 2 * B, Tmax, step, (flags & FY_STREAMING) != 0, flags, st, packed ? &pk : nullptr));
+        if (packed) hipLaunchKernelGGL(packed_euler_k, dim3(Tmax, B), dim3(128), 0, st, f->x, f->v, f->pk_tab, Tmax, C, f->dt_of_step[step], c.cfg_rate);
+        else hipLaunchKernelGGL(euler_k, dim3(Tmax, B), dim3(128), 0, st, f->x, f->v, d_T, Tmax, C, f->dt_of_step[step], c.cfg_rate, 0, 0);
     }
     // mel[b] = x[b][pmel:, :]^T in the reference's (B, 80, F) layout, flow.py:401
     for (int b = 0; b < B; ++b) {

@@ -62,6 +62,21 @@ def stream_poll_plan(n_tokens: Sequence[int], n_prompt_tokens: Sequence[int], to
     return polls
 
 
+def packed_rows(T: Sequence[int]):
+    """The layout of a packed call (FY_PACKED, include/fy_cosy3.h) as a pure function of the utterances' mel rows T[b] (prompt +
+    generated frames): the 2 B sequences - 2 b the conditional one of utterance b, 2 b + 1 its CFG branch - lie back to back in
+    that order, T[b] rows each, frame after frame.  -> (offsets, Mp): sequence 2 b + s starts at compact row offsets[2 b + s],
+    and Mp = 2 sum(T) rows go through the DiT blocks."""
+    offsets, Mp = [], 0
+    for b, t in enumerate(T):
+        t = int(t)
+        if t < 1:
+            raise ValueError(f"utterance {b} has no rows (T = {t})")
+        offsets += [Mp, Mp + t]
+        Mp += 2 * t
+    return offsets, Mp
+
+
 def _cfg_struct(cfg: FlowCfg) -> _lib.FlowConfig:
     c = _lib.FlowConfig()
     _lib.lib().fy_flow_default_config(C.byref(c))
@@ -108,7 +123,8 @@ class FlowEngine:
 
     def inference(self, token: torch.Tensor, n_token: Sequence[int], prompt_token: torch.Tensor, n_prompt: Sequence[int],
                   prompt_feat: torch.Tensor, n_pfeat: Sequence[int], embedding: torch.Tensor, rand_noise: torch.Tensor,
-                  flags: int = 0, streaming: bool = False, finalize: bool = True, incremental: bool = False) -> torch.Tensor:
+                  flags: int = 0, streaming: bool = False, finalize: bool = True, incremental: bool = False,
+                  packed: bool = False) -> torch.Tensor:
         """token (B, Nmax) int32, prompt_token (B, Pmax) int32, prompt_feat (B, PMmax, 80), embedding (B, 192),
         rand_noise (1|-, 80, >=T) -> mel (B, 80, 2*max(n_token)); utterance b is valid in [:, :, :2*n_token[b]].
         streaming / finalize as in the reference (flow.py:358-403): the chunk attention mask, and the last
@@ -116,7 +132,11 @@ class FlowEngine:
         incremental (with streaming, finalize=False, one utterance): this call extends the previous incremental call of the handle -
         only the new rows go through the DiT blocks (FY_INCREMENTAL; `stream_reset` starts a new stream).  Same result.  Works in
         the default arithmetic and with flags=FY_PRECISE (a call in the other arithmetic than the kept rows' starts over); with
-        FY_DIRECT the call is computed whole."""
+        FY_DIRECT the call is computed whole.
+        packed: a ragged batch sends only its valid rows through the DiT blocks (FY_PACKED; `packed_rows` is the layout,
+        `last_rows` tells what ran).  Same result, bit for bit; with one utterance or equal lengths it is the padded call."""
+        if packed:
+            flags |= _lib.FY_PACKED
         if incremental:
             flags |= _lib.FY_INCREMENTAL
         if streaming:
@@ -147,6 +167,17 @@ class FlowEngine:
     def weight_planes(self) -> int:
         """1: the weights were bf16-representable; 2: a general fp32 checkpoint (lo planes kept for FY_PRECISE)."""
         return int(_lib.lib().fy_flow_weight_planes(self._h))
+
+    @property
+    def last_rows(self) -> int:
+        """Rows the last `inference` call pushed through each DiT block's products: 2 B Tmax padded, 2 sum(T) packed,
+        2 (T - T0) for an incremental call; 0 before any call."""
+        return int(_lib.lib().fy_flow_last_rows(self._h))
+
+    @property
+    def ln_fold(self) -> bool:
+        """Whether the handle built the folded LayerNorm-modulate tables at create (fy_flow_ln_fold)."""
+        return int(_lib.lib().fy_flow_ln_fold(self._h)) == 1
 
     def stream_reset(self):
         """Forget what incremental calls have kept: the next one starts a new stream."""

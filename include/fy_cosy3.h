@@ -82,6 +82,20 @@ int fy_stream_destroy(void* stream);
                              the flag).  source must be null.                                                                          */
 #define FY_NO_FINALIZE 8u /* flow, HiFT: a streaming chunk (finalize=False in the reference): the last tokens / frames are
                             look-ahead context, not output (flow: pre_lookahead tokens; HiFT: 3 + 4 frames and 480 samples) */
+#define FY_PACKED 32u /* fy_flow_infer on a ragged batch: same inputs, output layout, capacities and results (bit for bit those of the
+                         call without the flag), but only the VALID rows of the 2 B sequences go through the DiT blocks, the final
+                         LayerNorm-modulate and the output projection - Mp = 2 sum_b T_b rows instead of 2 B Tmax.  The front (token
+                         embedding, look-ahead, input projection, the two position convolutions) keeps the padded (2 B, Tmax) layout;
+                         its valid rows are then gathered into one compact run, sequence 2 b + s behind sequence 2 b + s - 1, frame
+                         after frame; attention addresses the sequences through a row table, the qkv product's rotary epilogue reads
+                         a table with one row per compact row, and the Euler / CFG update reads the estimator's rows through the
+                         table and writes the state in the padded layout.  Works in the default arithmetic (LayerNorm fold on or
+                         off, as the handle chose at create), with FY_PRECISE (1 or 2 weight planes), FY_DIRECT, FY_STREAMING and
+                         FY_NO_FINALIZE.  Ignored by FY_INCREMENTAL calls that extend a stream (B = 1); a call with B = 1 or with all
+                         lengths equal takes the padded path, whose row count is the same.  The first packed call of a handle
+                         allocates its row, sequence and rotary tables (272 B per row of 2 max_batch max_frames, all or nothing:
+                         FY_ERR_HIP with the byte count, before any device work, and the handle stays usable without the flag).
+                         fy_dit_estimator and fy_flow_infer_streams do not take the flag.  fy_flow_last_rows tells which path ran. */
 
 /* ================================ HiFT vocoder ================================
  * replaces CausalHiFTGenerator.inference(speech_feat, finalize=True)
@@ -195,6 +209,10 @@ void fy_flow_destroy(fy_flow* f);
  * on the exact fp32 kernel), so it meets the reference's estimator-swap bar (export_onnx.py:109) on such weights too; the default
  * bf16 mode uses the hi plane only.  The step-dependent modulation vectors computed at create use both planes in either mode.     */
 int fy_flow_weight_planes(const fy_flow* f);
+/* 1: the handle built the folded LayerNorm-modulate tables at create (the default arithmetic's full-attention calls then fold the
+ * LayerNorm of the qkv and ff1 products into them); 0: it did not (FY_FLOW_LN_FOLD=0, shapes, or not enough free memory at create);
+ * -1: null handle.                                                                                                              */
+int fy_flow_ln_fold(const fy_flow* f);
 
 /* token (B, tok_ld) int32, prompt_token (B, ptok_ld) int32, prompt_feat (B, pfeat_rows, 80) fp32,
  * embedding (B, 192) fp32 - device; n_token / n_prompt / n_pfeat - host int32[B];
@@ -204,6 +222,11 @@ int fy_flow_infer(fy_flow* f, const int32_t* token, int32_t tok_ld, const int32_
                   int32_t ptok_ld, const int32_t* n_prompt, const float* prompt_feat, int32_t pfeat_rows, const int32_t* n_pfeat,
                   const float* embedding, const float* rand_noise, int32_t noise_ld, int32_t B, float* mel, int32_t mel_frames,
                   uint32_t flags, void* stream);
+
+/* Rows the last fy_flow_infer call of the handle pushed through the products of each DiT block: 2 B Tmax for a padded call (Tmax:
+ * the call's longest utterance, prompt + generated frames), 2 sum_b T_b for a packed one (FY_PACKED), 2 (T - T0) for an
+ * FY_INCREMENTAL call that extended T0 kept rows to T.  0 before any call; -1 for a null handle.                                  */
+int64_t fy_flow_last_rows(const fy_flow* f);
 
 /* forget what FY_INCREMENTAL calls have kept: the next one starts a new stream (call it when a stream=True generation begins) */
 int fy_flow_stream_reset(fy_flow* f);
