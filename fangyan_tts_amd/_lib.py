@@ -5,6 +5,7 @@ and every call checks the status code and raises FyError with fy_last_error().
 """
 import ctypes as C
 import os
+import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libfy_cosy3.so")
@@ -138,6 +139,7 @@ def _declare(L):
     L.fy_llm_slots_live.argtypes = [vp, i32p]
     L.fy_llm_slots_steps.argtypes = [vp]
     L.fy_llm_slots_steps.restype = C.c_int64
+    L.fy_llm_slots_export.argtypes = [vp, i32p, i32, vp, i32, vp, i32p, vp]
     L.fy_prompt_mel_create.argtypes = [C.POINTER(vp), i32, vp]
     L.fy_prompt_mel_destroy.argtypes = [vp]
     L.fy_prompt_mel_destroy.restype = None
@@ -191,6 +193,21 @@ HOST_WAIT_SLEEP_S = 2e-4          # stream_wait's poll interval; fy_set_host_wai
 
 def host_wait_spin() -> bool:
     return os.environ.get("FY_HOST_WAIT_SPIN", "0") == "1"
+
+
+_host_wait_users, _host_wait_mu = 0, threading.Lock()
+
+
+def host_wait_sleep(on: bool):
+    """Callers that share the process-wide host-wait mode (fy_set_host_wait) without owning every lane - `tts_serve` holds one -
+    count themselves in and out: the first one in switches the sleeping waits on, the last one out puts the spinning default back."""
+    global _host_wait_users
+    with _host_wait_mu:
+        _host_wait_users += 1 if on else -1
+        if on and _host_wait_users == 1:
+            check(lib().fy_set_host_wait(0 if host_wait_spin() else 1, int(HOST_WAIT_SLEEP_S * 1e6)))
+        elif not on and _host_wait_users == 0:
+            lib().fy_set_host_wait(0, int(HOST_WAIT_SLEEP_S * 1e6))
 
 
 def stream_wait(stream):

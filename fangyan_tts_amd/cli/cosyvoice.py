@@ -194,6 +194,46 @@ class CosyVoice3:
             model_input = self.frontend.frontend_instruct2(i, instruct_text, prompt_wav, self.sample_rate, zero_shot_spk_id)
             yield from self._run(model_input, i, stream, speed)
 
+    def inference_serve(self, items, **serve_kw):
+        """A queue of non-stream requests through `CosyVoice3Model.tts_serve` (the LM's decode slots refilled as they fall free,
+        ragged groups to the flow decoder + vocoder).  items: an iterable of (mode, kwargs) with mode "zero_shot" | "instruct2" |
+        "cross_lingual" and kwargs those of the matching inference_* method (no stream / speed); it may yield None for
+        "nothing has arrived yet".  The frontend runs per item exactly as in those methods, one request per text segment.
+        Yields tts_serve's items (completion order) with "item" (position in `items`) and "segment" added; serve_kw: steps_per_poll,
+        group_max, group_wait, keep_on_device."""
+        where = []                                           # request index -> (item, segment)
+
+        def requests():
+            k = 0
+            for it in items:
+                if it is None:
+                    yield None
+                    continue
+                mode, kw = it
+                kw = dict(kw)
+                tf = kw.pop("text_frontend", True)
+                tts_text = kw.pop("tts_text")
+                if mode == "zero_shot":
+                    if "<|endofprompt|>" not in kw["prompt_text"] + tts_text:
+                        logging.warning("<|endofprompt|> not found in CosyVoice3 inference, check your input text")
+                    kw["prompt_text"] = self.frontend.text_normalize(kw["prompt_text"], split=False, text_frontend=tf)
+                for j, seg in enumerate(self.frontend.text_normalize(tts_text, split=True, text_frontend=tf)):
+                    if mode == "zero_shot":
+                        mi = self.frontend.frontend_zero_shot(seg, kw["prompt_text"], kw["prompt_wav"], self.sample_rate, kw.get("zero_shot_spk_id", ""))
+                    elif mode == "instruct2":
+                        mi = self.frontend.frontend_instruct2(seg, kw["instruct_text"], kw["prompt_wav"], self.sample_rate, kw.get("zero_shot_spk_id", ""))
+                    elif mode == "cross_lingual":
+                        mi = self.frontend.frontend_cross_lingual(seg, kw["prompt_wav"], self.sample_rate, kw.get("zero_shot_spk_id", ""))
+                    else:
+                        raise ValueError(f"inference_serve: unknown mode {mode!r}")
+                    where.append((k, j))
+                    yield mi
+                k += 1
+
+        for out in self.model.tts_serve(requests(), **serve_kw):
+            out["item"], out["segment"] = where[out["index"]]
+            yield out
+
     def inference_instruct(self, *a, **kw):
         raise AssertionError("inference_instruct is only implemented for CosyVoice!")           # cli/cosyvoice.py:118-119
 

@@ -836,6 +836,230 @@ class CosyVoice3Model:
                 ln.hift.close_streams()
             self._release_lane(ln)
 
+    # ------------------------------------------------------------------ non-stream serving loop over the LM's decode slots
+    @torch.inference_mode()
+    def tts_serve(self, requests: Iterable[Optional[Dict[str, torch.Tensor]]], steps_per_poll: int = 8, group_max: Optional[int] = None,
+                  group_wait: int = 2, keep_on_device: bool = False, record_polls: bool = False):
+        """A queue of non-stream requests through ONE lane with every stage busy: requests join the LM's decode slots as slots
+        fall free, the slots that ended leave as ragged groups for the flow decoder + vocoder, which run on a worker thread and the
+        lane's stream while the LM goes on stepping on a stream of its own.  The schedule is `llm.ServeSchedule` (what
+        `llm.plan_serve` computes from lengths); this loop only carries it out.
+
+        requests: an iterable of model_input dicts (the keys `tts_batch` takes).  It is read at the start of every poll until it
+        yields None ("nothing more has arrived yet, poll on") or ends; a generator that waits for its source should yield None
+        instead of blocking, or the slots wait with it.
+        One poll: ONE join of the waiting requests into the lowest free slots; `steps_per_poll` token steps; the slots seen ended
+        are exported (`LlmEngine.export`: one copy kernel, their ids as a flow batch) and released; the ready requests are cut
+        into groups of up to `group_max` (default: the flow engine's max_batch), a smaller one once its oldest member has waited
+        `group_wait` polls or nothing else is under way; each group's token tensor is its own and goes to the worker behind an
+        event on the LM stream.  Groups go through `_token2wav`: flow_packed, flow_flags and hift_flags apply.
+        Yields, in completion order, {"index": position among the requests, "tts_speech": (1, S) (CPU unless keep_on_device),
+        "tokens": its ids (int32, on the device), "group": the indices that shared its flow + vocoder call, in batch order};
+        a request that exceeds the model's capacity, or for which the LM emitted no token, yields {"index", "error"} and the
+        loop goes on.  Greedy ids are those of `tts_batch([request])`.  Under "ras" the lane's uniforms are drawn once per call,
+        and a request consumes the row of the slot it joins from the start (as `tts_stream_batch`'s stream i consumes row i):
+        what it draws depends on its slot, and two requests that pass through one slot draw the same values.
+        `last_serve` keeps counters only (polls, joins, groups, token steps, flow calls and the rows they ran), so a call whose
+        `requests` never ends holds no growing state; record_polls=True also keeps, under "polls", `plan_serve`'s record of every poll
+        in which something happened (a join, token steps, a retirement, a group) - for tests and probes over a finite input.
+        A poll that did nothing at all (no slot occupied, nothing collected) sleeps for one host-wait interval, or waits that long
+        for the worker when a group is in flight: a generator that yields None for hours costs no core.
+        Closing the generator early releases every slot, joins the worker and frees the lane."""
+        import queue
+        import threading as th
+        import time
+        from .. import _lib as _lib_w
+        from ..llm import ServeSchedule
+        dev = self.device
+        z = torch.zeros(1, 0, dtype=torch.int32)
+        ln = self._acquire_lane()
+        lm, worker, stop, mode_was, session, sleeping = ln.llm, None, th.Event(), None, False, False
+        work_q, res_q = queue.Queue(), queue.Queue()
+        stats = {"n_polls": 0, "n_joins": 0, "n_groups": 0, "token_steps": 0, "flow_rows": 0, "flow_calls": 0}
+        if record_polls:
+            stats["polls"] = []
+        self.last_serve = stats
+        try:
+            n_slots = min(self.max_batch, lm.max_batch)
+            gmax = min(ln.flow.max_batch, ln.hift.max_batch) if group_max is None else int(group_max)
+            assert 1 <= gmax <= min(ln.flow.max_batch, ln.hift.max_batch), "group_max exceeds the lane's flow decoder / vocoder batch"
+            assert steps_per_poll >= 1 and group_wait >= 0
+            sch = ServeSchedule(n_slots, gmax, group_wait)
+            flow_stream, lm_stream = self._pipe_streams(2)
+            if ln.stream is not None:
+                flow_stream = ln.stream
+            here = torch.cuda.current_stream(dev)
+            lm_stream.wait_stream(here)
+            flow_stream.wait_stream(here)
+            mode_was = lm.decode_mode
+            lm.set_decode_mode(2)                             # the few-CU persistent step, as tts_pipeline beside its flow decoders
+            _lib_w.host_wait_sleep(True)
+            sleeping = True
+
+            def job():
+                try:
+                    with torch.inference_mode(), torch.cuda.device(dev):
+                        while True:
+                            item = work_q.get()
+                            if item is None:
+                                return
+                            if stop.is_set():
+                                continue
+                            members, inputs, toks, n_tok, ev = item
+                            with torch.cuda.stream(flow_stream):
+                                flow_stream.wait_event(ev)      # the export and the group's rows are complete on the LM stream
+                                wav, samples = self._token2wav(inputs, toks, n_tok, 1.0, ln)
+                                rows = ln.flow.last_rows
+                                if keep_on_device:
+                                    _lib_w.stream_wait(flow_stream)
+                                    res = wav
+                                else:
+                                    res = wav.cpu()
+                            res_q.put((members, res, samples, toks, n_tok, rows))
+                except BaseException as e:                      # surfaces in the consumer
+                    res_q.put(e)
+
+            worker = th.Thread(target=job, name="fy-serve-flow", daemon=True)
+            worker.start()
+            it = iter(requests)
+            inputs_of: Dict[int, Dict[str, torch.Tensor]] = {}
+            exported = {}                                       # request -> (the poll's export tensor, its row, its count)
+            n_seen, exhausted, in_flight = 0, False, 0
+
+            def results(wait: float):
+                """What the worker has finished -> result items; waits up to `wait` seconds for the first one (an exception of the
+                worker is raised here)."""
+                nonlocal in_flight
+                out, t_end = [], time.monotonic() + wait
+                while in_flight:
+                    try:
+                        r = res_q.get(timeout=min(0.05, wait)) if wait > 0 and not out else res_q.get_nowait()
+                    except queue.Empty:
+                        if out or time.monotonic() >= t_end:
+                            break
+                        if not worker.is_alive() and res_q.empty():
+                            raise RuntimeError("tts_serve: the flow worker ended without a result")
+                        continue
+                    if isinstance(r, BaseException):
+                        raise r
+                    in_flight -= 1
+                    members, res, samples, toks, n_tok, rows = r
+                    stats["flow_rows"] += rows
+                    stats["flow_calls"] += 1
+                    for j, i in enumerate(members):
+                        out.append({"index": i, "tts_speech": res[j: j + 1, : samples[j]], "tokens": toks[j, : n_tok[j]], "group": members})
+                return out
+
+            with self._lane_stream_of(lm_stream):
+                self._arm_lane_sampler(ln, self._next_batch_ids(), n_slots)
+                lm.open_slots(self.max_tokens)
+                session = True
+            while not (exhausted and sch.idle):
+                items = []
+                while not exhausted:                            # what has arrived since the last poll
+                    try:
+                        with torch.inference_mode(False):      # the caller's code (a frontend) makes ordinary tensors: the prompt
+                            d = next(it)                       # cache keys on their version counters
+                    except StopIteration:
+                        exhausted = True
+                        break
+                    if d is None:
+                        break
+                    i, n_seen = n_seen, n_seen + 1
+                    try:
+                        self._check_capacity([d], None)
+                    except ValueError as e:
+                        items.append({"index": i, "error": e})
+                        continue
+                    inputs_of[i] = d
+                    sch.arrive(i)
+                with self._lane_stream_of(lm_stream):
+                    joins = sch.join()
+                    if joins:
+                        ds = [inputs_of[r] for r, _ in joins]
+                        lm.join([s for _, s in joins], [d["text"].reshape(-1).tolist() for d in ds],
+                                [d.get("prompt_text", z).reshape(-1).tolist() for d in ds],
+                                [d.get("llm_prompt_speech_token", z).reshape(-1).tolist() for d in ds])
+                    steps, retired = 0, []
+                    if sch.occupied:
+                        steps = steps_per_poll
+                        n, fin = lm.step(steps)
+                        ended = {s: n[s] for s in sch.occupied if fin[s]}
+                        if ended:
+                            order = sorted(ended)
+                            toks, counts = lm.export(order, max(1, max(ended.values())))
+                            for s in order:
+                                lm.release(s)
+                            retired = sch.retire(ended)
+                            for row, (r, s) in enumerate(retired):
+                                if counts[row] < 1:
+                                    sch.drop(r)
+                                    inputs_of.pop(r)
+                                    items.append({"index": r, "error": RuntimeError("the language model emitted no speech token for an utterance")})
+                                else:
+                                    exported[r] = (toks, row, counts[row])
+                    groups = sch.cut(not exhausted)
+                    for g in groups:
+                        src = [exported.pop(r) for r in g]
+                        n_tok = [c for _, _, c in src]
+                        if all(t is src[0][0] for t, _, _ in src) and [row for _, row, _ in src] == list(range(src[0][0].shape[0])):
+                            gt = src[0][0]                      # the poll's export is the group, in its order
+                        else:                                   # the group's own tensor: its members' rows, longest first
+                            gt = torch.zeros(len(g), max(n_tok), dtype=torch.int32, device=dev)
+                            for j, (t, row, c) in enumerate(src):
+                                gt[j, :c] = t[row, :c]
+                        ev = torch.cuda.Event()
+                        ev.record(lm_stream)
+                        work_q.put((g, [inputs_of.pop(r) for r in g], gt, n_tok, ev))
+                        in_flight += 1
+                    busy = bool(joins or steps or retired or groups)
+                    if busy and record_polls:
+                        stats["polls"].append({"poll": sch.poll, "joins": joins, "steps": steps, "retired": retired, "groups": groups})
+                    stats["n_polls"] += 1
+                    stats["n_joins"] += len(joins)
+                    stats["n_groups"] += len(groups)
+                    if steps:
+                        stats["token_steps"] = lm.slot_steps
+                    sch.next_poll()
+                # with no slot running the loop has nothing to do but wait: for the worker when a group is in flight (up to 2 ms, so
+                # an arrival is not kept waiting for a whole group), else for the next arrival, one host-wait interval at a time
+                items += results(0.002 if steps == 0 else 0.0)
+                if not busy and not items:
+                    time.sleep(_lib_w.HOST_WAIT_SLEEP_S)
+                for item in items:
+                    yield item
+            while in_flight:
+                for item in results(3600.0):
+                    yield item
+        finally:
+            stop.set()
+            if worker is not None:
+                work_q.put(None)
+                worker.join()
+            try:
+                if session:
+                    with self._lane_stream_of(lm_stream):
+                        for s in lm.live():                     # an abandoned generator: cancelled requests
+                            lm.release(s)
+                    _lib_w.stream_wait(lm_stream)               # the handles' next calls may come on another stream
+                    _lib_w.stream_wait(flow_stream)
+                if mode_was is not None:
+                    lm.set_decode_mode(mode_was)
+                if sleeping:
+                    _lib_w.host_wait_sleep(False)
+            finally:
+                self._release_lane(ln)
+
+    def _lane_stream_of(self, st):
+        """`st` as the current stream of this thread for the engine calls inside (never held across a yield)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            with torch.cuda.device(self.device), torch.cuda.stream(st):
+                yield
+        return cm()
+
     # ------------------------------------------------------------------ reference-shaped path
     def tts(self, text=torch.zeros(1, 0, dtype=torch.int32), flow_embedding=torch.zeros(0, 192), llm_embedding=torch.zeros(0, 192),
             prompt_text=torch.zeros(1, 0, dtype=torch.int32), llm_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),

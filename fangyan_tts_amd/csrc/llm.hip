@@ -500,6 +500,23 @@ __global__ void slot_free_k(int* __restrict__ st, int mb, int slot) {
         if (slot < 0 || b == slot) st[i] = r == 3 ? 1 : 0;
     }
 }
+// fy_llm_slots_export: row i of tokens = the ids slot a.slot[i] has kept so far, zeros beyond them; counts[i] = its n_out.  The slot
+// numbers travel as kernel arguments (no table is copied).  Block (i, y) writes columns y * 256 + tid, + gridDim.y * 256, ... of row i.
+constexpr int kSlotExportMax = 256;
+struct SlotExportArgs {
+    int n = 0;
+    int slot[kSlotExportMax];
+};
+__global__ __launch_bounds__(256) void slots_export_k(SlotExportArgs a, const int* __restrict__ st, int mb, const int32_t* __restrict__ out_ids,
+                                                      int out_ld, int32_t* __restrict__ tokens, int ld, int32_t* __restrict__ counts) {
+    const int i = blockIdx.x;
+    if (i >= a.n) return;
+    const int s = a.slot[i], cnt = st[2 * mb + s];
+    const int keep = min(cnt, min(ld, out_ld));
+    for (int p = blockIdx.y * 256 + threadIdx.x; p < ld; p += gridDim.y * 256)
+        tokens[(long)i * ld + p] = p < keep ? out_ids[(long)s * out_ld + p] : 0;
+    if (blockIdx.y == 0 && threadIdx.x == 0) counts[i] = cnt;
+}
 
 // act[r][i] = silu(gu[r][2i]) * gu[r][2i+1]: the gate / up rows are interleaved (Qwen2MLP: down(silu(gate(x)) * up(x)))
 // planes != null: as three bf16 planes [3][n] instead of fp32 (two columns per thread)
@@ -1199,6 +1216,37 @@ extern "C" int fy_llm_slot_release(fy_llm* l, int32_t slot, void* stream) {
     hipLaunchKernelGGL(slot_free_k, dim3(1), dim3(256), 0, (hipStream_t)stream, l->st, l->max_batch, slot);
     HIP_TRY(hipGetLastError());
     l->slot_state[slot] = 0;
+    return FY_OK;
+}
+
+// The ids of n occupied slots as one (n, ld) batch + counts: one launch on the session's stream, ordered behind the steps that wrote
+// the ids and ahead of whatever join follows.  The counts live on the device only (the host knows a slot's state, not its length),
+// so a row longer than ld is clamped and counts[i] says so.
+extern "C" int fy_llm_slots_export(fy_llm* l, const int32_t* slots, int32_t n, int32_t* tokens, int32_t ld, int32_t* counts,
+                                   int32_t* counts_host, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(l && slots && tokens && counts, FY_ERR_ARG, "fy_llm_slots_export: null argument");
+    FY_CHECK(l->slots_open, FY_ERR_STATE, "fy_llm_slots_export: no slot session is open (call fy_llm_slots_open first)");
+    FY_CHECK(n >= 1 && n <= l->max_batch, FY_ERR_ARG, "fy_llm_slots_export: %d slots outside [1, %d]", n, l->max_batch);
+    FY_CHECK(n <= kSlotExportMax, FY_ERR_ARG, "fy_llm_slots_export: %d slots, one call takes up to %d", n, kSlotExportMax);
+    FY_CHECK(ld >= 1, FY_ERR_ARG, "fy_llm_slots_export: ld %d below 1", ld);
+    SlotExportArgs a;
+    a.n = n;
+    for (int j = 0; j < n; ++j) {
+        const int s = slots[j];
+        FY_CHECK(s >= 0 && s < l->max_batch, FY_ERR_ARG, "fy_llm_slots_export: slot %d outside [0, %d)", s, l->max_batch);
+        for (int i = 0; i < j; ++i) FY_CHECK(slots[i] != s, FY_ERR_ARG, "fy_llm_slots_export: slot %d named twice", s);
+        FY_CHECK(l->slot_state[s] != 0, FY_ERR_STATE, "fy_llm_slots_export: slot %d is free", s);
+        a.slot[j] = s;
+    }
+    for (int j = n; j < kSlotExportMax; ++j) a.slot[j] = 0;
+    hipLaunchKernelGGL(slots_export_k, dim3(n, std::min(8, cdiv(ld, 256))), dim3(256), 0, st, a, l->st, l->max_batch, l->slot_out, l->slot_out_ld,
+                       tokens, ld, counts);
+    HIP_TRY(hipGetLastError());
+    if (counts_host) {
+        HIP_TRY(hipMemcpyAsync(counts_host, counts, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(stream_wait(st));
+    }
     return FY_OK;
 }
 

@@ -59,6 +59,102 @@ def grouped_steps(raw_lengths: Sequence[int], n_slots: int, steps_per_poll: int 
     return t
 
 
+class ServeSchedule:
+    """Every decision of the serving loop (`CosyVoice3Model.tts_serve`), as host state without a GPU: which request joins which
+    slot, and which retired requests form the next flow group.  `plan_serve` drives it with forced lengths, `tts_serve` with what
+    the device reports; neither decides anything else.  One poll is: `arrive` for the requests that came in, `join`, the token
+    steps (the caller's), `retire` for the slots seen ended, `cut`, `next_poll`."""
+
+    def __init__(self, n_slots: int, group_max: int, group_wait: int):
+        assert n_slots >= 1 and group_max >= 1 and group_wait >= 0
+        self.n_slots, self.group_max, self.group_wait = int(n_slots), int(group_max), int(group_wait)
+        self.pending: deque = deque()             # requests that arrived and hold no slot yet, in arrival order
+        self.occupied: Dict[int, int] = {}        # slot -> request
+        self.ready: List[Tuple[int, int, int]] = []   # (request, length, poll it retired in), oldest first
+        self.poll = 0
+
+    def arrive(self, request: int):
+        self.pending.append(request)
+
+    def join(self) -> List[Tuple[int, int]]:
+        """The poll's one join: waiting requests in arrival order into the lowest free slots -> [(request, slot)]."""
+        batch = _fill_slots([s for s in range(self.n_slots) if s not in self.occupied], self.pending)
+        self.occupied.update({s: r for r, s in batch})
+        return batch
+
+    def retire(self, ended: Dict[int, int]) -> List[Tuple[int, int]]:
+        """ended: {slot seen ended in this poll: its token count}.  The slots are free again; their requests enter the ready
+        list in ascending slot order -> [(request, slot)] in that order."""
+        out = []
+        for s in sorted(ended):
+            r = self.occupied.pop(s)
+            self.ready.append((r, int(ended[s]), self.poll))
+            out.append((r, s))
+        return out
+
+    def drop(self, request: int):
+        """Take a retired request out of the ready list (it cannot be decoded: no token)."""
+        self.ready = [e for e in self.ready if e[0] != request]
+
+    def cut(self, more_coming: bool) -> List[Tuple[int, ...]]:
+        """The flow groups this poll forms, oldest first: `group_max` ready requests make a group; what is left goes as one
+        group once its oldest member has waited `group_wait` polls, or once nothing is running, waiting for a slot or still to
+        arrive.  Inside a group the longest comes first (requests of equal length in retirement order)."""
+        groups = []
+        while len(self.ready) >= self.group_max:
+            groups.append(self.ready[: self.group_max])
+            self.ready = self.ready[self.group_max:]
+        if self.ready and (self.poll - self.ready[0][2] >= self.group_wait or not (self.occupied or self.pending or more_coming)):
+            groups.append(self.ready)
+            self.ready = []
+        return [tuple(r for r, _, _ in sorted(g, key=lambda e: -e[1])) for g in groups]
+
+    def next_poll(self):
+        self.poll += 1
+
+    @property
+    def idle(self) -> bool:
+        return not (self.pending or self.occupied or self.ready)
+
+
+def plan_serve(n_tokens: Sequence[int], arrivals: Optional[Sequence[int]], n_slots: int, steps_per_poll: int = 8, group_max: int = 8,
+               group_wait: int = 2, lengths: Optional[Sequence[int]] = None):
+    """The schedule `CosyVoice3Model.tts_serve` runs when request r arrives in poll arrivals[r] (non-decreasing; None: all in
+    poll 0; the input ends with its last arrival) and emits exactly n_tokens[r] tokens (as `plan_slots`: the join emits the first,
+    so it needs n_tokens[r] - 1 token steps; a request that ends on a stop token needs one step more than it emits).  lengths:
+    the counts the groups are sorted by (after the silent-token filter); default n_tokens.  A pure function, no GPU.
+    Poll p: the requests with arrivals[r] <= p wait for a slot; ONE join puts them into the lowest free slots in arrival order;
+    `steps_per_poll` token steps run if any slot is occupied; the slots seen ended are exported and released, their requests wait
+    in the ready list; `ServeSchedule.cut` forms the flow groups.
+    -> one dict per poll: {"poll", "joins": [(request, slot)], "steps", "retired": [(request, slot)], "groups": [(request, ...)]}.
+    With every request present at poll 0 the token steps (the sum of "steps") are `plan_slots`' for the same lengths."""
+    N = len(n_tokens)
+    arrivals = [0] * N if arrivals is None else [int(a) for a in arrivals]
+    lengths = n_tokens if lengths is None else lengths
+    assert len(arrivals) == N and len(lengths) == N and steps_per_poll >= 1 and all(int(n) >= 1 for n in n_tokens)
+    assert all(a >= 0 for a in arrivals) and all(arrivals[i] <= arrivals[i + 1] for i in range(N - 1)), "arrival polls in request order"
+    sch = ServeSchedule(n_slots, group_max, group_wait)
+    left: Dict[int, int] = {}                 # slot -> token steps its request still needs
+    nxt, polls = 0, []
+    while nxt < N or not sch.idle:
+        while nxt < N and arrivals[nxt] <= sch.poll:
+            sch.arrive(nxt)
+            nxt += 1
+        joins = sch.join()
+        for r, s in joins:
+            left[s] = int(n_tokens[r]) - 1
+        steps = steps_per_poll if sch.occupied else 0
+        ended = {}
+        if steps:
+            ended = {s: int(lengths[sch.occupied[s]]) for s, n in left.items() if n <= steps_per_poll}
+            left = {s: n - steps_per_poll for s, n in left.items() if n > steps_per_poll}
+        retired = sch.retire(ended)
+        groups = sch.cut(nxt < N)
+        polls.append({"poll": sch.poll, "joins": joins, "steps": steps, "retired": retired, "groups": groups})
+        sch.next_poll()
+    return polls
+
+
 class LlmEngine:
     """weights: the llm.pt state_dict (reference key names, fp32 CUDA tensors; lm_head not needed).
     weight_planes: 0 (default) = the library chooses - two bf16 planes per matrix (w = hi + lo) exactly when some weight is not
@@ -206,6 +302,21 @@ class LlmEngine:
     def release(self, slot: int):
         """Free a slot, ended or not (a cancelled request)."""
         check(_lib.lib().fy_llm_slot_release(self._h, int(slot), self._stream()))
+
+    def export(self, slots: Sequence[int], ld: Optional[int] = None):
+        """The ids of the occupied slots `slots` as one ragged batch for `FlowEngine.inference` (fy_llm_slots_export: one copy
+        kernel on the current stream, no host copy of the id matrix) -> (tokens (len(slots), ld) int32 CUDA, a fresh tensor whose
+        row i holds slot slots[i]'s ids and zeros beyond them; counts, a host list).  ld defaults to the session's out_ld; a row
+        with more than ld ids is cut to ld and its count says so.  The slots may be released and joined again at once."""
+        n = len(slots)
+        if ld is None:                                       # (no session: the library says so)
+            ld = self._gen[0].shape[1] if getattr(self, "_gen", None) else 1
+        ld = int(ld)
+        tokens = torch.empty(max(n, 1), max(ld, 1), dtype=torch.int32, device=self.device)
+        counts = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        host = (C.c_int32 * max(n, 1))()
+        check(_lib.lib().fy_llm_slots_export(self._h, _lib.int_array(slots), n, tokens.data_ptr(), ld, counts.data_ptr(), host, self._stream()))
+        return tokens, list(host)
 
     def live(self) -> List[int]:
         """The occupied slots of the session (running, or ended and not yet released)."""

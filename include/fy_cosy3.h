@@ -365,6 +365,19 @@ int fy_llm_slot_join_embeds(fy_llm* l, const int32_t* slots, int32_t n, const vo
 int fy_llm_slot_release(fy_llm* l, int32_t slot, void* stream);
 int fy_llm_slots_live(const fy_llm* l, int32_t* state);
 int64_t fy_llm_slots_steps(const fy_llm* l);
+/* The hand-off from the slots to the flow decoder: the ids of the n occupied slots `slots` (host int32[n], distinct; ended or still
+ * running - a running slot gives its ids so far) as ONE ragged batch in fy_flow_infer's token layout, by one copy kernel on
+ * `stream` (the session's): row i of tokens (device, (n, ld) int32) receives slot slots[i]'s emitted ids (after the silent-token
+ * filter), zeros from its count to ld; counts (device int32[n]) receives the slots' out_n; counts_host (nullable, host int32[n])
+ * the same after a wait on the stream in the host-wait mode in effect (fy_set_host_wait).  The slot numbers travel as kernel
+ * arguments (up to 256 per call); nothing passes through the host.  The copy is ordered on the stream behind the steps that wrote
+ * the ids and ahead of later calls, so the slots may be released and joined again at once; `tokens` never aliases the session's
+ * out_ids.  A slot's count lives on the device only, so ld cannot be checked against it: a row whose count exceeds ld is CLAMPED
+ * to its first ld ids and counts[i] still reports the full count (counts[i] > ld says the row was cut).  Before any device work,
+ * the session as it was: FY_ERR_STATE - no session open, a listed slot is free; FY_ERR_ARG - a slot out of range or listed twice,
+ * n outside [1, min(max_batch, 256)], ld < 1, a null pointer.                                                                      */
+int fy_llm_slots_export(fy_llm* l, const int32_t* slots, int32_t n, int32_t* tokens, int32_t ld, int32_t* counts,
+                        int32_t* counts_host, void* stream);
 /* Sampler used by the following fy_llm_generate, fy_llm_begin / fy_llm_prefill + fy_llm_step and slot-session calls.
  * kind 0: the greedy rule above.  kind 1: the reference's default,
  * repetition-aware sampling (utils/common.py:137-166 `ras_sampling` with top_p, top_k, win_size, tau_r = 0.8, 25, 10, 0.1 in
