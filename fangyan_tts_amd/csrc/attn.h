@@ -38,6 +38,8 @@ int dit_attention_split_tab(const bf16_t* qkv_hi, const bf16_t* qkv_lo, bf16_t* 
 int llm_attention(const float* q, int q_ld, const float* Kc, const float* Vc, const int* row_seq, const int* row_pos, float* out,
                   int o_ld, int R, int Hq, int Hk, int max_ctx, hipStream_t st);
 
-// decode step: RoPE of q / new k, cache append and attention over 0..row_pos[r] in one launch (qkv raw, fp32)
+// decode step: RoPE of q / new k, cache append and attention over 0..row_pos[r] in one launch (qkv raw, fp32).  form: 0 = the
+// launcher's rule (the group kernel when Hq / Hk <= 8 and its LDS fits, else the per-head kernel - which is what the default
+// max_ctx of 1730 gets); 1 / 2 = the per-head / the group kernel whatever the rule says (the test hooks; FY_ERR_ARG if it cannot run)
 int llm_attention_step(const float* qkv, float* Kc, float* Vc, const int* row_seq, const int* row_pos, const float* inv_freq,
-                       float* out, int o_ld, int R, int Hq, int Hk, int max_ctx, hipStream_t st, bf16_t* img = nullptr);
+                       float* out, int o_ld, int R, int Hq, int Hk, int max_ctx, hipStream_t st, bf16_t* img = nullptr, int form = 0);

@@ -791,14 +791,17 @@ __global__ __launch_bounds__(512) void llm_attention_step_gqa_k(const float* __r
 }
 
 int llm_attention_step(const float* qkv, float* Kc, float* Vc, const int* row_seq, const int* row_pos, const float* inv_freq,
-                       float* out, int o_ld, int R, int Hq, int Hk, int max_ctx, hipStream_t st, bf16_t* img) {
-    FY_CHECK(qkv && Kc && Vc && row_seq && row_pos && inv_freq && (out || img) && R >= 1 && Hq % Hk == 0, FY_ERR_ARG, "llm_attention_step: bad arguments");
+                       float* out, int o_ld, int R, int Hq, int Hk, int max_ctx, hipStream_t st, bf16_t* img, int form) {
+    FY_CHECK(qkv && Kc && Vc && row_seq && row_pos && inv_freq && (out || img) && R >= 1 && Hq % Hk == 0 && form >= 0 && form <= 2, FY_ERR_ARG,
+             "llm_attention_step: bad arguments");
     {
         // one block per (row, kv head) when the group fits a block's waves (FY_LLM_ATTN_GQA=0: the per-head kernel)
         static const int gqa = getenv("FY_LLM_ATTN_GQA") ? atoi(getenv("FY_LLM_ATTN_GQA")) : 1;
         const int grp = Hq / Hk;
         const size_t lds_g = (640 + (((size_t)grp * max_ctx + 3) & ~(size_t)3) + GQ_CH * 64) * sizeof(float) + 8 * 192 * sizeof(bf16_t);
-        if (gqa && grp <= 8 && lds_g <= 64 * 1024) {
+        const bool fits = grp <= 8 && lds_g <= 64 * 1024;
+        FY_CHECK(form != 2 || fits, FY_ERR_ARG, "llm_attention_step: the group kernel cannot run %d heads per kv head at context %d", grp, max_ctx);
+        if (form == 2 || (form == 0 && gqa && fits)) {
             hipLaunchKernelGGL(llm_attention_step_gqa_k, dim3(R, Hk), dim3(512), lds_g, st, qkv, Kc, Vc, row_seq, row_pos, inv_freq, out, o_ld, Hq, Hk,
                                max_ctx, 0.125f, img);
             HIP_TRY(hipGetLastError());

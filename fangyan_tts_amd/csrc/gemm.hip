@@ -1363,7 +1363,9 @@ __device__ __forceinline__ frag_ab ld_frag_nt(const bf16_t* p) {
 }
 
 // split one fp32 value exactly into three bf16 terms (hardware round-to-nearest-even converts)
+// (no contraction: the residual is that of the fp32 value f, not of an unrounded product f came from - gemv32.h: gv32_split3)
 __device__ __forceinline__ void split3(float f, uint32_t& h, uint32_t& m, uint32_t& l) {
+#pragma clang fp contract(off)
     __bf16 hb = (__bf16)f;
     float r1 = f - (float)hb;
     __bf16 mb = (__bf16)r1;

@@ -56,7 +56,10 @@ __device__ __forceinline__ long gv32_off(int K16, int row, int col0, int plane) 
     const int z = row >> 5, r = row & 31, kk = col0 >> 4, half = (col0 >> 3) & 1, j = col0 & 7;
     return ((((long)z * K16 + kk) * 3 + plane) * 64 + half * 32 + r) * 16 + j * 2;
 }
+// Contraction is OFF: where f arrives as a product (norm weight x activation), a fused multiply-subtract would take the residual
+// f - hi of the UNROUNDED product, and the planes would no longer add up to the fp32 value f that every other path sees.
 __device__ __forceinline__ void gv32_split3(float f, unsigned& h, unsigned& m, unsigned& l) {
+#pragma clang fp contract(off)
     __bf16 hb = (__bf16)f;
     float r1 = f - (float)hb;
     __bf16 mb = (__bf16)r1;
