@@ -100,6 +100,9 @@ def _declare(L):
     L.fy_hift_stream_slot_reset.argtypes = [vp, i32]
     L.fy_hift_stream_slot_samples.argtypes = [vp, i32]
     L.fy_hift_stream_slot_window.argtypes = [vp, i32]
+    L.fy_hift_streams_store.argtypes = [vp, i32]
+    L.fy_hift_stream_slot_push.argtypes = [vp, i32p, i32, f32p, i32, i32p, i32p, vp]
+    L.fy_hift_stream_slot_frames.argtypes = [vp, i32]
     L.fy_hift_infer_streams.argtypes = [vp, i32p, i32, C.POINTER(vp), i32p, i32p, i32p, f32p, f32p, f32p, i32, i32p, u32, vp]
     L.fy_flow_default_config.argtypes = [C.POINTER(FlowConfig)]
     L.fy_flow_default_config.restype = None

@@ -194,13 +194,16 @@ class CosyVoice3:
             model_input = self.frontend.frontend_instruct2(i, instruct_text, prompt_wav, self.sample_rate, zero_shot_spk_id)
             yield from self._run(model_input, i, stream, speed)
 
-    def inference_serve(self, items, **serve_kw):
+    def inference_serve(self, items, stream=False, **serve_kw):
         """A queue of non-stream requests through `CosyVoice3Model.tts_serve` (the LM's decode slots refilled as they fall free,
         ragged groups to the flow decoder + vocoder).  items: an iterable of (mode, kwargs) with mode "zero_shot" | "instruct2" |
         "cross_lingual" and kwargs those of the matching inference_* method (no stream / speed); it may yield None for
         "nothing has arrived yet".  The frontend runs per item exactly as in those methods, one request per text segment.
         Yields tts_serve's items (completion order) with "item" (position in `items`) and "segment" added; serve_kw: steps_per_poll,
-        group_max, group_wait, keep_on_device."""
+        group_max, group_wait, keep_on_device.
+        stream=True: the requests go through `CosyVoice3Model.tts_serve_stream` instead - every request a stream=True generation
+        that joins a slot when one is free and delivers its audio chunk by chunk; yields that loop's items ("index", "chunk",
+        "final", "tts_speech") with "item" and "segment" added; serve_kw: n_slots, tokens_per_poll, keep_on_device."""
         where = []                                           # request index -> (item, segment)
 
         def requests():
@@ -230,7 +233,7 @@ class CosyVoice3:
                     yield mi
                 k += 1
 
-        for out in self.model.tts_serve(requests(), **serve_kw):
+        for out in (self.model.tts_serve_stream if stream else self.model.tts_serve)(requests(), **serve_kw):
             out["item"], out["segment"] = where[out["index"]]
             yield out
 

@@ -1050,6 +1050,173 @@ class CosyVoice3Model:
             finally:
                 self._release_lane(ln)
 
+    # ------------------------------------------------------------------ streaming serving loop: stream=True requests join slots over time
+    @torch.inference_mode()
+    def tts_serve_stream(self, requests: Iterable[Optional[Dict[str, torch.Tensor]]], n_slots: Optional[int] = None, tokens_per_poll: int = 25,
+                         keep_on_device: bool = False, record_polls: bool = False):
+        """A queue of stream=True requests that arrive over time through ONE lane: slot i is slot i of the LM's decode-slot
+        session, of the flow decoder's stream-slot session and of the vocoder's, a request joins the lowest free slot and starts
+        delivering audio after its first hop of tokens, and a slot whose stream has ended is joined again in the next poll.  The
+        schedule is `flow.ServeStreamSchedule` (what `flow.plan_serve_stream` computes from lengths); this loop only carries it out.
+
+        requests: as for `tts_serve` - an iterable of model_input dicts, read at the start of every poll until it yields None
+        ("nothing yet") or ends.  n_slots defaults to max_batch.
+        One poll: ONE join of the waiting requests (their flow and vocoder slots are reset); `tokens_per_poll` token steps; ONE
+        `LlmEngine.export` of the ids so far of the streams that get a chunk or their final pass; ONE
+        `FlowEngine.inference_streams` for the chunks and ONE batched final `FlowEngine.inference` (flow_packed applies) for the
+        streams that ended; after each flow call ONE `HiftEngine.stream_slot_push` moves its new frames into the vocoder's mel store
+        on the device; ONE `HiftEngine.inference_streams` on the stores vocodes all of them; the ended slots are released.  The LM
+        handle runs in decode mode 2 for the duration.  flow_flags / hift_flags apply.
+        Yields {"index": position among the requests, "chunk": 0, 1, .., "final": bool, "tts_speech": (1, S) (CPU unless
+        keep_on_device)}; a request's chunks come in order and are those `tts(**request, stream=True)` yields for it alone (the
+        chunk boundaries follow its token count, `flow.stream_chunk_plan`).  A request over the model's capacity, or for which
+        the LM emitted no token, yields {"index", "error"} and the loop goes on.  Under "ras" the lane's uniforms are drawn once per
+        call and a request consumes the row of the slot it joins from the start, as in `tts_serve`.
+        `last_serve_stream` keeps counters only (n_polls, n_joins, token_steps, chunk_passes, final_passes, pushes);
+        record_polls=True also keeps, under "polls", `plan_serve_stream`'s record of every poll.  A poll with nothing to do sleeps
+        one host-wait interval.  Closing the generator early releases every slot, closes both stream sessions, puts the decode
+        mode back and frees the lane."""
+        import time
+        from .. import _lib as _lib_w
+        from ..flow import ServeStreamSchedule
+        dev = self.device
+        z = torch.zeros(1, 0, dtype=torch.int32)
+        look, hop = self.cfg.flow.pre_lookahead, self.token_hop_len
+        ln = self._acquire_lane()
+        lm, mode_was, session = ln.llm, None, False
+        stats = {"n_polls": 0, "n_joins": 0, "token_steps": 0, "chunk_passes": 0, "final_passes": 0, "pushes": 0}
+        if record_polls:
+            stats["polls"] = []
+        self.last_serve_stream = stats
+        try:
+            most = min(self.max_batch, lm.max_batch, ln.flow.max_batch, ln.hift.max_batch)
+            n_slots = most if n_slots is None else int(n_slots)
+            assert 1 <= n_slots <= most, "n_slots exceeds the lane's LM / flow decoder / vocoder batch"
+            assert tokens_per_poll >= 1
+            sch = ServeStreamSchedule(n_slots, tokens_per_poll, hop, look)
+            pm_max = max(2 * self.max_prompt_tokens, 1)
+            with self._lane_stream(ln):
+                mode_was = lm.decode_mode
+                lm.set_decode_mode(2)
+                self._arm_lane_sampler(ln, self._next_batch_ids(), n_slots)
+                lm.open_slots(self.max_tokens)
+                session = True
+                ln.flow.open_streams(n_slots, 2 * (self.max_tokens + self.max_prompt_tokens), precise=bool(self.flow_flags & FY_PRECISE))
+                ln.hift.open_streams(n_slots, store_frames=2 * self.max_tokens)
+                # the flow prompt of the request in slot s: row s of these, written at its join
+                ptok = torch.zeros(n_slots, max(self.max_prompt_tokens, 1), dtype=torch.int32, device=dev)
+                pfeat = torch.zeros(n_slots, pm_max, 80, device=dev)
+                emb = torch.zeros(n_slots, self.cfg.flow.spk_in, device=dev)
+            it = iter(requests)
+            inputs_of: Dict[int, Dict[str, torch.Tensor]] = {}
+            seat: Dict[int, List[int]] = {}                     # slot -> [request, prompt tokens, prompt mel rows, chunks yielded]
+            n_seen, exhausted = 0, False
+            while True:
+                items = []
+                while not exhausted:                            # what has arrived since the last poll
+                    try:
+                        with torch.inference_mode(False):
+                            d = next(it)
+                    except StopIteration:
+                        exhausted = True
+                        break
+                    if d is None:
+                        break
+                    i, n_seen = n_seen, n_seen + 1
+                    try:
+                        self._check_capacity([d], None)
+                        if d["prompt_speech_feat"].reshape(-1, 80).shape[0] > pm_max:
+                            raise ValueError(f"utterance 0: {d['prompt_speech_feat'].reshape(-1, 80).shape[0]} prompt mel frames, the model "
+                                             f"was built for max_prompt_tokens={self.max_prompt_tokens} (2 frames per token)")
+                    except ValueError as e:
+                        items.append({"index": i, "error": e})
+                        continue
+                    inputs_of[i] = d
+                    sch.arrive(i, d["flow_prompt_speech_token"].reshape(-1).shape[0])
+                if exhausted and sch.idle and not items:
+                    break
+                joins, chunks, released = [], [], []
+                with self._lane_stream(ln):
+                    joins = sch.join()
+                    if joins:
+                        ds = [inputs_of.pop(r) for r, _ in joins]
+                        lm.join([s for _, s in joins], [d["text"].reshape(-1).tolist() for d in ds],
+                                [d.get("prompt_text", z).reshape(-1).tolist() for d in ds],
+                                [d.get("llm_prompt_speech_token", z).reshape(-1).tolist() for d in ds])
+                        for (r, s), d in zip(joins, ds):
+                            fp, pf = d["flow_prompt_speech_token"].reshape(-1).to(torch.int32), d["prompt_speech_feat"].reshape(-1, 80).float()
+                            ptok[s, : fp.shape[0]] = fp.to(dev)
+                            pfeat[s, : pf.shape[0]] = pf.to(dev)
+                            emb[s] = d["flow_embedding"].reshape(-1).float().to(dev)
+                            ln.flow.stream_slot_reset(s)
+                            ln.hift.stream_slot_reset(s)
+                            seat[s] = [r, fp.shape[0], pf.shape[0], 0]
+                    if sch.occupied:
+                        n, fin = lm.step(tokens_per_poll)
+                        stats["token_steps"] = lm.slot_steps
+                        for s in sorted(sch.occupied):
+                            if fin[s] and n[s] < 1:
+                                items.append({"index": sch.occupied[s], "error": RuntimeError("the language model emitted no speech token for an utterance")})
+                                lm.release(s)
+                                sch.release(s)
+                                released.append(s)
+                                del seat[s]
+                        chunks, slots, freed = sch.chunks({s: (n[s], fin[s]) for s in sch.occupied})
+                        released = sorted(released + freed)
+                    if chunks:
+                        ready = [(s, c) for s, c in zip(slots, chunks) if not c[3]]
+                        ended = [(s, c) for s, c in zip(slots, chunks) if c[3]]
+                        order = [s for s, _ in ready + ended]
+                        # the ids so far of every stream of the poll as ONE (n, ld) batch: the chunks' rows first, then the final passes'
+                        tok, _ = lm.export(order, max(c[1] for c in chunks))
+                        for grp, final in ((ready, False), (ended, True)):
+                            if not grp:
+                                continue
+                            ss, n_in = [s for s, _ in grp], [c[1] for _, c in grp]
+                            rows = tok[len(ready):] if final else tok[: len(ready)]
+                            ix = torch.tensor(ss, device=dev)
+                            prompt = (ptok[ix], [seat[s][1] for s in ss], pfeat[ix], [seat[s][2] for s in ss], emb[ix])
+                            if final:
+                                mel = ln.flow.inference(rows, n_in, *prompt, self.rand_noise, flags=self.flow_flags, packed=self.flow_packed)
+                                stats["final_passes"] += 1
+                            else:
+                                mel = ln.flow.inference_streams(ss, rows, n_in, *prompt, self.rand_noise, flags=self.flow_flags)
+                                stats["chunk_passes"] += 1
+                            # the call's new frames go to the vocoder's stores on the device: tokens [offset, n_in - look) (the final pass: to n_in)
+                            ln.hift.stream_slot_push(ss, mel, [2 * c[2] for _, c in grp], [2 * ((c[1] if final else c[1] - look) - c[2]) for _, c in grp])
+                            stats["pushes"] += 1
+                        wavs = ln.hift.inference_streams(order, None, self.rand_ini, self.sine_noise, [c[3] for _, c in ready + ended],
+                                                         flags=self.hift_flags)
+                        for (s, c), w in zip(ready + ended, wavs):
+                            items.append({"index": seat[s][0], "chunk": seat[s][3], "final": bool(c[3]),
+                                          "tts_speech": w[None] if keep_on_device else w[None].cpu()})
+                            seat[s][3] += 1
+                        for s, _ in ended:
+                            lm.release(s)
+                            del seat[s]
+                if record_polls:
+                    stats["polls"].append({"joins": joins, "chunks": chunks, "released": released})
+                stats["n_polls"] += 1
+                stats["n_joins"] += len(joins)
+                busy = bool(joins or sch.occupied or chunks)
+                sch.next_poll()
+                if not busy and not items:
+                    time.sleep(_lib_w.HOST_WAIT_SLEEP_S)
+                for item in items:
+                    yield item
+        finally:
+            try:
+                if session:
+                    with self._lane_stream(ln):
+                        for s in lm.live():                     # an abandoned generator: cancelled requests
+                            lm.release(s)
+                        ln.flow.close_streams()
+                        ln.hift.close_streams()
+                if mode_was is not None:
+                    lm.set_decode_mode(mode_was)
+            finally:
+                self._release_lane(ln)
+
     def _lane_stream_of(self, st):
         """`st` as the current stream of this thread for the engine calls inside (never held across a yield)."""
         import contextlib

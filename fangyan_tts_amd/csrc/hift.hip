@@ -55,6 +55,11 @@ struct fy_hift {
     int* ss_tab = nullptr;
     int ss_pitch = 0;
     size_t ss_bytes = 0;
+    // the session's mel store (fy_hift_streams_store): (n_slots, mel, ss_cap) fp32, a slot's frames contiguous per channel as in the
+    // mel a call reads; ss_held[slot]: frames pushed so far (host)
+    float* ss_store = nullptr;
+    int ss_cap = 0;
+    std::vector<int> ss_held;
     int L(int stage, int F) const {                  // rows of stage tensors for F frames
         int l = F;
         for (int i = 0; i <= stage; ++i) l *= cfg.ups[i];
@@ -86,6 +91,7 @@ static void source_down_shape(const fy_hift_config& c, int i, int* k, int* strid
 fy_hift::~fy_hift() {
     if (ss_phase) (void)hipFree(ss_phase);
     if (ss_tab) (void)hipFree(ss_tab);
+    if (ss_store) (void)hipFree(ss_store);
     conv_free(w.conv_pre); conv_free(w.conv_post);
     for (int i = 0; i < N_UP; ++i) { conv_free(w.ups[i]); conv_free(w.source_downs[i]); conv_free(sd_mfma[i]); conv_free(ups_poly[i]); }
     for (int i = 0; i < 5; ++i) conv_free(w.f0c[i]);
@@ -983,8 +989,10 @@ extern "C" int fy_hift_streams_close(fy_hift* h) {
     FY_CHECK(h, FY_ERR_ARG, "fy_hift_streams_close: null handle");
     if (h->ss_phase) (void)hipFree(h->ss_phase);
     if (h->ss_tab) (void)hipFree(h->ss_tab);
+    if (h->ss_store) (void)hipFree(h->ss_store);
     h->ss_phase = nullptr; h->ss_tab = nullptr; h->ss_pitch = 0; h->ss_bytes = 0;
-    h->ss.clear();
+    h->ss_store = nullptr; h->ss_cap = 0;
+    h->ss.clear(); h->ss_held.clear();
     return FY_OK;
 }
 
@@ -1003,7 +1011,77 @@ extern "C" int fy_hift_streams_open(fy_hift* h, int32_t n_slots) {
     }
     h->ss_pitch = pitch; h->ss_bytes = pb + tb;
     h->ss.assign(n_slots, fy_hift::Slot());      // (a slot's sums are read only after a call of the slot has stored them)
+    h->ss_held.assign(n_slots, 0);
     return FY_OK;
+}
+
+// ---- the session's mel store: the flow decoder's output stays on the device between the two stages --------------------------------
+extern "C" int fy_hift_streams_store(fy_hift* h, int32_t cap_frames) {
+    FY_CHECK(h, FY_ERR_ARG, "fy_hift_streams_store: null handle");
+    FY_CHECK(!h->ss.empty(), FY_ERR_STATE, "fy_hift_streams_store: no stream-slot session is open (fy_hift_streams_open)");
+    FY_CHECK(cap_frames >= 1, FY_ERR_ARG, "fy_hift_streams_store: cap_frames %d below 1", cap_frames);
+    const size_t was = h->ss_store ? (size_t)h->ss.size() * h->cfg.mel * h->ss_cap * sizeof(float) : 0;
+    const size_t nb = (size_t)h->ss.size() * h->cfg.mel * (size_t)cap_frames * sizeof(float);
+    if (h->ss_store) (void)hipFree(h->ss_store);
+    h->ss_store = nullptr; h->ss_cap = 0; h->ss_bytes -= was;
+    std::fill(h->ss_held.begin(), h->ss_held.end(), 0);
+    if (hipMalloc(&h->ss_store, nb) != hipSuccess) {
+        (void)hipGetLastError();
+        h->ss_store = nullptr;
+        fy_set_error("fy_hift_streams_store: hipMalloc(%zu B) failed (%d slots x %d channels x %d frames)", nb, (int)h->ss.size(), h->cfg.mel,
+                     cap_frames);
+        return FY_ERR_HIP;
+    }
+    h->ss_cap = cap_frames; h->ss_bytes += nb;
+    return FY_OK;
+}
+
+// Row i of a push: count[i] frames of every channel from src row i (C, ld) at frame first[i] to slot[i]'s store at frame held[i].
+// The per-row values are kernel arguments (as SlotExportArgs in llm.hip): no table upload, no host wait.  One wave per block walks
+// 64 consecutive frames of one channel; plain dword loads and stores (first[i] need not be 16-byte aligned).
+constexpr int kMelPushMax = 128;
+struct MelPushArgs { int slot[kMelPushMax], first[kMelPushMax], count[kMelPushMax], held[kMelPushMax]; };
+__global__ __launch_bounds__(64) void mel_push_k(MelPushArgs a, const float* __restrict__ src, int ld, float* __restrict__ store, int C, int cap) {
+    const int i = blockIdx.z, c = blockIdx.y, f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= a.count[i]) return;
+    store[((long)a.slot[i] * C + c) * cap + a.held[i] + f] = src[((long)i * C + c) * ld + a.first[i] + f];
+}
+
+extern "C" int fy_hift_stream_slot_push(fy_hift* h, const int32_t* slots, int32_t n, const float* mel, int32_t mel_ld, const int32_t* first,
+                                        const int32_t* count, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    FY_CHECK(h && slots && mel && first && count, FY_ERR_ARG, "fy_hift_stream_slot_push: null argument");
+    FY_CHECK(!h->ss.empty(), FY_ERR_STATE, "fy_hift_stream_slot_push: no stream-slot session is open (fy_hift_streams_open)");
+    FY_CHECK(h->ss_store, FY_ERR_STATE, "fy_hift_stream_slot_push: the session has no mel store (fy_hift_streams_store)");
+    const int n_slots = (int)h->ss.size();
+    FY_CHECK(n >= 1 && n <= n_slots && n <= kMelPushMax, FY_ERR_ARG, "fy_hift_stream_slot_push: %d rows outside [1, %d] (the session's slots, %d per launch)",
+             n, std::min(n_slots, kMelPushMax), kMelPushMax);
+    FY_CHECK(mel_ld >= 1, FY_ERR_ARG, "fy_hift_stream_slot_push: mel_ld %d below 1", mel_ld);
+    MelPushArgs a;
+    int most = 0;
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        FY_CHECK(s >= 0 && s < n_slots, FY_ERR_ARG, "fy_hift_stream_slot_push: slots[%d] = %d outside the session's %d slots", i, s, n_slots);
+        for (int j = 0; j < i; ++j) FY_CHECK(slots[j] != s, FY_ERR_ARG, "fy_hift_stream_slot_push: slot %d is listed twice", s);
+        FY_CHECK(count[i] >= 0, FY_ERR_ARG, "fy_hift_stream_slot_push: count[%d] = %d is negative", i, count[i]);
+        FY_CHECK(first[i] >= 0 && (long)first[i] + count[i] <= mel_ld, FY_ERR_ARG,
+                 "fy_hift_stream_slot_push: row %d reads frames [%d, %ld) of a mel of %d (mel_ld)", i, first[i], (long)first[i] + count[i], mel_ld);
+        FY_CHECK((long)h->ss_held[s] + count[i] <= h->ss_cap, FY_ERR_ARG,
+                 "fy_hift_stream_slot_push: slot %d would hold %ld frames, the store has room for %d (cap_frames)", s, (long)h->ss_held[s] + count[i],
+                 h->ss_cap);
+        a.slot[i] = s; a.first[i] = first[i]; a.count[i] = count[i]; a.held[i] = h->ss_held[s];
+        most = std::max(most, count[i]);
+    }
+    if (most > 0) {
+        hipLaunchKernelGGL(mel_push_k, dim3(cdiv(most, 64), h->cfg.mel, n), dim3(64), 0, st, a, mel, mel_ld, h->ss_store, h->cfg.mel, h->ss_cap);
+        HIP_TRY(hipGetLastError());
+    }
+    for (int i = 0; i < n; ++i) h->ss_held[slots[i]] += count[i];
+    return FY_OK;
+}
+
+extern "C" int fy_hift_stream_slot_frames(const fy_hift* h, int32_t slot) {
+    return h && slot >= 0 && slot < (int)h->ss_held.size() ? h->ss_held[slot] : -1;
 }
 
 extern "C" int64_t fy_hift_streams_bytes(const fy_hift* h) { return h ? (int64_t)h->ss_bytes : 0; }
@@ -1011,6 +1089,7 @@ extern "C" int64_t fy_hift_streams_bytes(const fy_hift* h) { return h ? (int64_t
 extern "C" int fy_hift_stream_slot_reset(fy_hift* h, int32_t slot) {
     FY_CHECK(h && slot >= 0 && slot < (int)h->ss.size(), FY_ERR_ARG, "fy_hift_stream_slot_reset: no slot %d (%d open)", slot, h ? (int)h->ss.size() : 0);
     h->ss[slot] = fy_hift::Slot();
+    h->ss_held[slot] = 0;
     return FY_OK;
 }
 
@@ -1046,8 +1125,11 @@ extern "C" int fy_hift_infer_streams(fy_hift* h, const int32_t* slots, int32_t n
                 FY_CHECK(s >= 0 && s < n_slots, FY_ERR_ARG, "fy_hift_infer_streams: slots[%d] = %d outside the session's %d slots", i, s, n_slots);
                 FY_CHECK(!seen[s], FY_ERR_ARG, "fy_hift_infer_streams: slot %d is listed twice", s);
                 seen[s] = 1;
-                FY_CHECK(mel[i] && frames[i] >= 1 && frames[i] <= mel_ld[i], FY_ERR_ARG, "fy_hift_infer_streams: frames[%d] = %d outside [1, %d] (mel_ld)",
+                FY_CHECK(frames[i] >= 1 && frames[i] <= mel_ld[i], FY_ERR_ARG, "fy_hift_infer_streams: frames[%d] = %d outside [1, %d] (mel_ld)",
                          i, frames[i], mel_ld[i]);
+                FY_CHECK(mel[i] || h->ss_store, FY_ERR_ARG, "fy_hift_infer_streams: mel[%d] is null and the session has no mel store (fy_hift_streams_store)", i);
+                FY_CHECK(mel[i] || frames[i] <= h->ss_held[s], FY_ERR_ARG, "fy_hift_infer_streams: frames[%d] = %d, slot %d's store holds %d", i, frames[i],
+                         s, h->ss_held[s]);
             }
             if ((mel_ld[i] > 4096) != (pass == 1)) continue;
             const fy_hift::Slot& sl = h->ss[slots[i]];
@@ -1089,8 +1171,10 @@ extern "C" int fy_hift_infer_streams(fy_hift* h, const int32_t* slots, int32_t n
         const Row& r = rows[b];
         fw[b] = r.Fw; fin[b] = r.fin;
         int* t = tab.data() + (size_t)b * SROW;
-        const unsigned long long p = (unsigned long long)(uintptr_t)mel[r.i];
-        t[SR_SLOT] = r.slot; t[SR_W] = r.W; t[SR_LD] = mel_ld[r.i]; t[SR_A0] = r.a0; t[SR_ANEXT] = r.a_next;
+        // a null mel reads the slot's store at the store's pitch; mel_ld[i] still picks the f0 convs' form, as for a pointer
+        const float* src = mel[r.i] ? mel[r.i] : h->ss_store + (size_t)r.slot * h->cfg.mel * h->ss_cap;
+        const unsigned long long p = (unsigned long long)(uintptr_t)src;
+        t[SR_SLOT] = r.slot; t[SR_W] = r.W; t[SR_LD] = mel[r.i] ? mel_ld[r.i] : h->ss_cap; t[SR_A0] = r.a0; t[SR_ANEXT] = r.a_next;
         t[SR_NLO] = (int)(r.S_prev - (long)r.W * up); t[SR_WAVROW] = r.i;
         t[SR_MEL_LO] = (int)(unsigned)(p & 0xffffffffull); t[SR_MEL_HI] = (int)(unsigned)(p >> 32);
         n_new[r.i] = (int)(r.S_out - r.S_prev);

@@ -4,7 +4,8 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence
+from collections import deque
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -59,6 +60,108 @@ def stream_poll_plan(n_tokens: Sequence[int], n_prompt_tokens: Sequence[int], to
                 poll.append((i, n_tokens[i], offset[i], True))
                 ended[i] = True
         polls.append(poll)
+    return polls
+
+
+class ServeStreamSchedule:
+    """Every decision of the streaming serving loop (`CosyVoice3Model.tts_serve_stream`), as host state without a GPU: which
+    request joins which slot, which chunk each stream gets in a poll and which slots fall free.  `plan_serve_stream` drives it
+    with forced lengths, the loop with what the device reports; neither decides anything else.  One poll is: `arrive` for the
+    requests that came in, `join`, the token steps (the caller's), `chunks` with the slots' counts, `next_poll`.
+    A stream is credited at most `tokens_per_poll` tokens per poll, the join's own first token included (the device, which steps
+    every slot `tokens_per_poll` times after the join, is one token ahead until it ends): the schedule of a stream is then
+    `stream_poll_plan`'s from the poll it joins in, a function of its final count alone."""
+
+    def __init__(self, n_slots: int, tokens_per_poll: int = 25, hop: int = 25, look: int = 3):
+        assert n_slots >= 1 and tokens_per_poll >= 1 and hop >= 1 and look >= 0
+        self.n_slots, self.tokens_per_poll, self.hop, self.look = int(n_slots), int(tokens_per_poll), int(hop), int(look)
+        self.pending: deque = deque()             # (request, prompt tokens) that arrived and hold no slot yet, in arrival order
+        self.occupied: Dict[int, int] = {}        # slot -> request
+        self._have: Dict[int, int] = {}           # slot -> tokens credited
+        self._offset: Dict[int, int] = {}         # slot -> tokens whose mel has been cut
+        self._pad: Dict[int, int] = {}
+        self._freed: List[int] = []               # released in this poll: free from the next one
+        self.poll = 0
+
+    def arrive(self, request: int, n_prompt_tokens: int):
+        self.pending.append((request, int(n_prompt_tokens)))
+
+    def join(self) -> List[Tuple[int, int]]:
+        """The poll's one join: waiting requests in arrival order into the lowest free slots -> [(request, slot)]."""
+        free = [s for s in range(self.n_slots) if s not in self.occupied and s not in self._freed]
+        batch = []
+        for s in free[: len(self.pending)]:
+            r, p = self.pending.popleft()
+            self.occupied[s] = r
+            self._have[s], self._offset[s], self._pad[s] = 0, 0, -(-p // self.hop) * self.hop - p
+            batch.append((r, s))
+        return batch
+
+    def need(self, slot: int) -> int:
+        """Tokens the slot's next streaming chunk takes in."""
+        o = self._offset[slot]
+        return o + (self.hop + self._pad[slot] if o == 0 else self.hop) + self.look
+
+    def chunks(self, counts: Dict[int, Tuple[int, bool]]):
+        """counts: {occupied slot: (tokens its LM has emitted, whether it has ended)}.  In ascending slot order, at most one entry
+        per stream: a streaming chunk when the credited tokens reach `need`, else the final pass when the LM has ended and every
+        token is credited; that slot is released.  -> ([(request, n_in, offset, finalize)], [slot of each entry], released)."""
+        out, slots, released = [], [], []
+        for s in sorted(self.occupied):
+            n, ended = counts[s]
+            self._have[s] = min(int(n), self._have[s] + self.tokens_per_poll)
+            need = self.need(s)
+            if self._have[s] >= need:
+                out.append((self.occupied[s], need, self._offset[s], False))
+                slots.append(s)
+                self._offset[s] = need - self.look
+            elif ended and self._have[s] == int(n):
+                out.append((self.occupied[s], int(n), self._offset[s], True))
+                slots.append(s)
+                released.append(s)
+        for s in released:
+            self.release(s)
+        return out, slots, released
+
+    def release(self, slot: int):
+        """The slot's stream is over (its final pass, or no token at all): free from the next poll on."""
+        del self.occupied[slot], self._have[slot], self._offset[slot], self._pad[slot]
+        self._freed.append(slot)
+
+    def next_poll(self):
+        self._freed = []
+        self.poll += 1
+
+    @property
+    def idle(self) -> bool:
+        return not (self.pending or self.occupied)
+
+
+def plan_serve_stream(n_tokens: Sequence[int], n_prompt_tokens: Sequence[int], arrivals: Optional[Sequence[int]], n_slots: int,
+                      tokens_per_poll: int = 25, hop: int = 25, look: int = 3):
+    """The schedule `CosyVoice3Model.tts_serve_stream` runs when request r arrives in poll arrivals[r] (non-decreasing; None: all
+    in poll 0) with n_prompt_tokens[r] flow prompt tokens and its LM emits exactly n_tokens[r] tokens.  A pure function, no GPU.
+    Poll p: the requests with arrivals[r] <= p wait in arrival order; ONE join puts them into the lowest free slots (the join emits
+    the first token); every occupied slot's LM gains tokens, `tokens_per_poll` per poll counted from the join; every stream then
+    gets at most one chunk - its next `stream_chunk_plan` entry once its tokens are there, the final pass in the poll that sees it
+    ended; a slot released in a poll can be joined in the next.
+    -> one dict per poll: {"joins": [(request, slot)], "chunks": [(request, n_in, offset, finalize)], "released": [slot]}; chunks in
+    ascending slot order.  With every request present at poll 0 and no more requests than slots the chunk lists are
+    `stream_poll_plan`'s."""
+    N = len(n_tokens)
+    arrivals = [0] * N if arrivals is None else [int(a) for a in arrivals]
+    assert len(arrivals) == N and len(n_prompt_tokens) == N and all(int(n) >= 1 for n in n_tokens)
+    assert all(a >= 0 for a in arrivals) and all(arrivals[i] <= arrivals[i + 1] for i in range(N - 1)), "arrival polls in request order"
+    sch = ServeStreamSchedule(n_slots, tokens_per_poll, hop, look)
+    nxt, polls = 0, []
+    while nxt < N or not sch.idle:
+        while nxt < N and arrivals[nxt] <= sch.poll:
+            sch.arrive(nxt, n_prompt_tokens[nxt])
+            nxt += 1
+        joins = sch.join()
+        chunks, _, released = sch.chunks({s: (int(n_tokens[r]), True) for s, r in sch.occupied.items()})
+        polls.append({"joins": joins, "chunks": chunks, "released": released})
+        sch.next_poll()
     return polls
 
 

@@ -109,9 +109,15 @@ class HiftEngine:
         return int(_lib.lib().fy_hift_stream_window(self._h))
 
     # ---- stream slots: several streams through one incremental pass (csrc/hift.hip: fy_hift_infer_streams)
-    def open_streams(self, n_slots: int):
-        """Give the handle `n_slots` (<= max_batch) incremental streams; the work buffers stay the handle's own."""
-        check(_lib.lib().fy_hift_streams_open(self._h, n_slots))
+    def open_streams(self, n_slots: int, store_frames: Optional[int] = None):
+        """Give the handle `n_slots` (<= max_batch) incremental streams; the work buffers stay the handle's own.
+        store_frames: also a mel store of that many frames per slot (n_slots x 80 x store_frames fp32, fy_hift_streams_store):
+        `stream_slot_push` appends a flow call's rows to it on the device and `inference_streams(..., mels=None)` reads it.  When
+        the device lacks the memory this raises FyError with the byte count and the session stays open without a store."""
+        with torch.cuda.device(self.device):
+            check(_lib.lib().fy_hift_streams_open(self._h, n_slots))
+            if store_frames is not None:
+                check(_lib.lib().fy_hift_streams_store(self._h, int(store_frames)))
 
     def close_streams(self):
         check(_lib.lib().fy_hift_streams_close(self._h))
@@ -131,20 +137,41 @@ class HiftEngine:
         """Mel frames of the slot's stream the last call ran through the network (-1: no such slot)."""
         return int(_lib.lib().fy_hift_stream_slot_window(self._h, slot))
 
-    def inference_streams(self, slots: Sequence[int], mels: Sequence[torch.Tensor], rand_ini: torch.Tensor, sine_noise: torch.Tensor,
-                          finalize: Sequence[bool], flags: int = 0):
+    def stream_slot_push(self, slots: Sequence[int], mel: torch.Tensor, first: Sequence[int], count: Sequence[int]):
+        """ONE copy kernel: row i of `mel` (n, 80, F) - a flow call's output - frames [first[i], first[i] + count[i]) go behind
+        what slot slots[i]'s store holds.  Nothing passes through the host; the slots' counts advance."""
+        n = len(slots)
+        assert mel.is_cuda and mel.dtype == torch.float32 and mel.dim() == 3 and mel.shape[0] == n and mel.shape[1] == self.cfg.mel
+        assert mel.is_contiguous() and len(first) == n and len(count) == n
+        check(_lib.lib().fy_hift_stream_slot_push(self._h, _lib.int_array(list(slots)), n, mel.data_ptr(), mel.shape[2], _lib.int_array(first),
+                                                  _lib.int_array(count), self._stream()))
+
+    def stream_slot_frames(self, slot: int) -> int:
+        """Mel frames the slot's store holds (-1: no such slot)."""
+        return int(_lib.lib().fy_hift_stream_slot_frames(self._h, slot))
+
+    def inference_streams(self, slots: Sequence[int], mels: Optional[Sequence[torch.Tensor]], rand_ini: torch.Tensor, sine_noise: torch.Tensor,
+                          finalize: Sequence[bool], flags: int = 0, frames: Optional[Sequence[int]] = None):
         """Continue the streams of `slots` in one pass.  mels[i]: (1, 80, F_i) or (80, F_i), stream i's whole mel so far (separate
         tensors of any lengths); finalize[i]: stream i's last call.  Returns a list of 1-D tensors, stream i's NEW samples
         [stream_slot_samples(slots[i]) before the call, 480 (F_i - 8) or 480 F_i) - views of one (n, wav_ld) buffer - the same
-        values `inference(..., incremental=True)` writes there for that stream alone."""
+        values `inference(..., incremental=True)` writes there for that stream alone.
+        mels=None: every stream's mel is what its slot's store holds (`stream_slot_push`) - all of it, or its first frames[i]
+        frames: the same samples, bit for bit, as the call given those frames as tensors."""
         n = len(slots)
-        assert n >= 1 and len(mels) == n and len(finalize) == n
-        ms = []
-        for m in mels:
-            m = m[0] if m.dim() == 3 else m
-            assert m.is_cuda and m.dtype == torch.float32 and m.dim() == 2 and m.shape[0] == self.cfg.mel
-            ms.append(m.contiguous())
-        frames = [int(m.shape[1]) for m in ms]
+        assert n >= 1 and len(finalize) == n
+        if mels is None:
+            frames = [self.stream_slot_frames(s) for s in slots] if frames is None else [int(f) for f in frames]
+            ptrs = (C.c_void_p * n)()
+        else:
+            assert len(mels) == n
+            ms = []
+            for m in mels:
+                m = m[0] if m.dim() == 3 else m
+                assert m.is_cuda and m.dtype == torch.float32 and m.dim() == 2 and m.shape[0] == self.cfg.mel
+                ms.append(m.contiguous())
+            frames = [int(m.shape[1]) for m in ms]
+            ptrs = (C.c_void_p * n)(*[m.data_ptr() for m in ms])
         up = self.cfg.upsample_total
         assert sine_noise.is_cuda and sine_noise.is_contiguous() and sine_noise.shape[-2] >= up * max(frames)
         # what each slot has delivered; a slot given fewer frames than its last call (samples / up + 8) starts over, as in the library
@@ -152,7 +179,6 @@ class HiftEngine:
         done = [d if F >= d // up + 8 else 0 for d, F in zip(done, frames)]
         wav_ld = max(1, max(stream_new_samples(F, bool(fin), d, up) for F, fin, d in zip(frames, finalize, done)))
         wav = torch.zeros(n, wav_ld, device=self.device, dtype=torch.float32)
-        ptrs = (C.c_void_p * n)(*[m.data_ptr() for m in ms])
         n_new = (C.c_int32 * n)()
         check(_lib.lib().fy_hift_infer_streams(self._h, _lib.int_array(list(slots)), n, ptrs, _lib.int_array(frames), _lib.int_array(frames),
                                                _lib.int_array([int(bool(f)) for f in finalize]), rand_ini.data_ptr(), sine_noise.data_ptr(),

@@ -163,9 +163,32 @@ int64_t fy_hift_streams_bytes(const fy_hift* h);
 int fy_hift_stream_slot_reset(fy_hift* h, int32_t slot);
 int fy_hift_stream_slot_samples(const fy_hift* h, int32_t slot);
 int fy_hift_stream_slot_window(const fy_hift* h, int32_t slot);
+/* The session's mel store: the flow decoder's output stays on the device between the two stages.  fy_hift_streams_store gives the
+ * open session ONE fp32 tensor (n_slots, 80, cap_frames) - slot s's mel so far, frames contiguous per channel at a pitch of
+ * cap_frames, the layout fy_hift_infer_streams reads - allocated at the call (FY_ERR_HIP with the byte count when the device does
+ * not have it: the session stays usable without a store); calling it again replaces the store and empties every slot.
+ * fy_hift_streams_close frees it, fy_hift_streams_bytes counts it (n_slots * 80 * cap_frames * 4 bytes more).  cap_frames has no
+ * upper limit of its own: a stream read from the store takes the f0 convolutions' form from mel_ld[i] as every stream does (see
+ * fy_hift_infer_streams), never from the store's pitch, so a store beyond 4096 frames changes no bit.
+ * fy_hift_stream_slot_push: ONE launch (mel_push_k) for the n listed rows (host int32 slots[n], distinct): row i copies
+ * mel[i, :, first[i] : first[i] + count[i]] of the device tensor mel (n, 80, mel_ld) - the output of fy_flow_infer_streams or
+ * fy_flow_infer - behind the frames slot slots[i] holds and advances its count.  first / count (host int32[n]) travel as kernel
+ * arguments (up to 128 rows per call): no table upload, no host wait; the copy is ordered on `stream` (the session's).  first[i]
+ * needs no alignment; count[i] = 0 is allowed (a call whose counts are all 0 launches nothing).
+ * fy_hift_stream_slot_frames: the frames slot holds (-1: no such slot); fy_hift_stream_slot_reset empties the slot.
+ * Before any device work, the session and every count as they were: FY_ERR_STATE - no session open, no store; FY_ERR_ARG - a slot
+ * out of range or listed twice, n outside [1, min(slots, 128)], count[i] < 0, first[i] < 0 or first[i] + count[i] > mel_ld, held +
+ * count[i] > cap_frames (the message names the count needed), a null pointer.                                                    */
+int fy_hift_streams_store(fy_hift* h, int32_t cap_frames);
+int fy_hift_stream_slot_push(fy_hift* h, const int32_t* slots, int32_t n, const float* mel, int32_t mel_ld, const int32_t* first,
+                             const int32_t* count, void* stream);
+int fy_hift_stream_slot_frames(const fy_hift* h, int32_t slot);
 /* Continue the streams in slots[0 .. n) (host int32, distinct) in ONE pass (the call implies FY_INCREMENTAL; flags: FY_DIRECT,
  * FY_PRECISE or 0).  mel[n]: host array of device pointers - stream i's whole mel so far, (80, mel_ld[i]) fp32, valid in
- * [0, frames[i]); the streams' mels are separate tensors of any lengths.  finalize[n] (host): per stream, nonzero = the
+ * [0, frames[i]); the streams' mels are separate tensors of any lengths.  mel[i] == NULL means slot slots[i]'s mel store
+ * (fy_hift_streams_store): frames[i] <= the frames the slot holds, rows are addressed at the store's pitch, and mel_ld[i] keeps
+ * its second role only - it selects the f0 convolutions' form (callers pass frames[i], as for a tensor of exactly that length);
+ * the samples are bit for bit those of the same call given a pointer to the same frames.  finalize[n] (host): per stream, nonzero = the
  * stream's last call (no look-ahead frames, nothing held back), 0 = a streaming chunk as under FY_NO_FINALIZE.  wav: (n, wav_ld)
  * fp32 - stream i's NEW samples [S_prev_i, S_out_i) land compact at row i from column 0, n_new[i] (host, out) of them; the rest
  * of the row is left untouched.  rand_ini / sine_noise as for fy_hift_infer, sine_noise at least 480 * max frames[i] rows.
@@ -177,7 +200,8 @@ int fy_hift_stream_slot_window(const fy_hift* h, int32_t slot);
  * stream across that length runs it from frame 0 (its phase sums came from the other form) and still writes only its new samples.
  * The samples are bit for bit those fy_hift_infer writes at [S_prev_i, S_out_i) for stream i alone on its whole mel.
  * FY_ERR_ARG (before any device work, the session as it was), with a message: no session open; a slot out of range or listed
- * twice; n above the session's slots; frames[i] outside [1, mel_ld[i]]; a streaming chunk below the 9-frame minimum; n x the
+ * twice; n above the session's slots; frames[i] outside [1, mel_ld[i]]; a null mel[i] without a store, or with frames[i] above
+ * the frames the slot holds; a streaming chunk below the 9-frame minimum; n x the
  * longest window above the handle's max_batch x max_frames frame rows; wav_ld below the largest n_new (the last two name the
  * count needed).                                                                                                              */
 int fy_hift_infer_streams(fy_hift* h, const int32_t* slots, int32_t n, const float* const* mel, const int32_t* mel_ld,
